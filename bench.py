@@ -3,6 +3,13 @@
 waveform -> token ids (mel frontend + encoder + KV-cached decode + stitch).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full             (+ every extra leg, check and roofline)
+    python bench.py --gpus N --steps K --warmup W --dump-outputs DIR (+ the last timed step's outputs as .npy)
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  Everything else the
+script measures or checks -- the host-PCM leg, the profiled per-kernel / per-stage passes and the
+roofline figures built on them, the frontend-alone leg, the CPU baseline, the beam-5 and large-v2
+legs, the token comparison with the committed oracle rows -- runs only with `--full`.
 
 One "step" = one pass of the hot path over one batch of synthetic input: `--seconds` (30) seconds
 of seeded synthetic 16 kHz audio PER GPU, cut into the reference's windows (14.9 s, 3 s overlap,
@@ -201,11 +208,31 @@ def profiled_passes(lib, _lib, decode_fn, n_prof):
     return [float(x) for x in buf], kstats
 
 
+def dump_outputs(dirname, tokens, per_window):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the stitched token ids
+    (tokens.npy) and every window's token row (window_tokens.npy, -1 past window_lens.npy) -- as float64 arrays
+    (token ids are exact there), so two builds can be compared output for output on the same seeded inputs."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = [[int(t) for t in r] for r in per_window]
+    win = np.full((len(rows), max((len(r) for r in rows), default=0)), -1.0, dtype=np.float64)
+    for i, r in enumerate(rows):
+        win[i, :len(r)] = r
+    np.save(os.path.join(dirname, "tokens.npy"), np.asarray([int(t) for t in tokens], dtype=np.float64))
+    np.save(os.path.join(dirname, "window_tokens.npy"), win)
+    np.save(os.path.join(dirname, "window_lens.npy"), np.asarray([len(r) for r in rows], dtype=np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed steps (default: a timed region of ~5 s)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra leg, check and roofline (host-PCM leg, profiled passes, frontend leg, CPU "
+                         "baseline, beam-5 and large-v2 legs, comparison with the committed oracle rows); off: the "
+                         "headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (stitched token ids, per-window token rows) as DIR/<name>.npy")
     ap.add_argument("--model", default="tiny.en")
     ap.add_argument("--seconds", type=float, default=None,
                     help="audio seconds per GPU per step (default 30; one full window = 29.91 with --geometry whisper30)")
@@ -215,16 +242,16 @@ def main() -> None:
                          "T = 2990 + 10 frames, C = 1500 encoder positions (wb_model_set_frame_limit)")
     ap.add_argument("--beam", type=int, default=1)
     ap.add_argument("--max-depth", type=int, default=100)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--mel-windows", type=int, default=256,
-                    help="batched windows of the frontend-alone leg (mel-frames/s; SURVEY 8d: >= 100)")
+                    help="batched windows of the frontend-alone leg (--full; mel-frames/s; SURVEY 8d: >= 100)")
     ap.add_argument("--large-v2-leg", default="auto", choices=["auto", "on", "off"],
-                    help="extra timed leg: large-v2, --large-v2-seconds of audio per GPU (BASELINE.json's 8-GPU headline is "
-                         "large-v2; the driver's command line cannot select a model).  auto = only when --gpus > 1; "
+                    help="extra timed leg of --full: large-v2, --large-v2-seconds of audio per GPU (BASELINE.json's 8-GPU "
+                         "headline is large-v2).  auto = with the greedy tiny.en reference-geometry run; "
                          "`value` stays the tiny.en figure in every case")
     ap.add_argument("--beam5-leg", default="auto", choices=["auto", "on", "off"],
-                    help="extra timed leg: the same workload with the reference's live beam_size 5 (auto: with the greedy "
-                         "reference-geometry run)")
+                    help="extra timed leg of --full: the same workload with the reference's live beam_size 5 (auto: with "
+                         "the greedy reference-geometry run)")
     ap.add_argument("--large-v2-seconds", type=float, default=450.0,
                     help="audio per GPU of the large-v2 leg (450 s = 38 windows = one GPU's share of the 8-GPU hour)")
     ap.add_argument("--dtype", default="f32", choices=["f32"],
@@ -234,6 +261,8 @@ def main() -> None:
                     help="encoder-side GEMMs of the f32 path: f32 = exact-f32 MFMA (default), split = three fp16 MFMAs per "
                          "product (f32-grade results, ~1.9x the rate); default: the library's (WHISPER_HIP_ENCODER_SPLIT)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.encoder is not None:                     # (read once per process by the library, at model load)
         os.environ["WHISPER_HIP_ENCODER_SPLIT"] = "1" if args.encoder == "split" else "0"
     if args.seconds is None:
@@ -321,6 +350,8 @@ def main() -> None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tokens, per_window)
 
     # what the process group actually looks like (so the driver's first SCALE line is self-checking): world size as
     # torch.distributed reports it, and every rank's device
@@ -337,7 +368,7 @@ def main() -> None:
     # `value` is measured with the inputs resident in HBM; this leg hands the library the host buffer and lets it upload the
     # rank's span inside the timed region, so the PCIe-inclusive figure stands next to it
     from_host = None
-    if args.steps >= 2:
+    if args.full and args.steps >= 2:
         host_pcm = np.ascontiguousarray(audio[span[0]:span[1]])
 
         def decode_local_host(lo, hi):
@@ -372,7 +403,7 @@ def main() -> None:
     roofline = None
     kernels = None
     stages = None
-    if rank == 0:
+    if args.full and rank == 0:
         n_prof = 3
         buf, kstats = profiled_passes(lib, _lib, lambda: decode_local(*local_win), n_prof)
         mel_ms, enc_ms, ckv_ms, dec_ms, n_steps, n_mel, logit_ms, n_logit = buf
@@ -417,7 +448,7 @@ def main() -> None:
 
     # ---- the frontend alone (BASELINE.json's second metric): >= 100 batched reference windows, PCM resident ----
     mel_frontend = None
-    if rank == 0:
+    if args.full and rank == 0:
         n_mw = max(1, args.mel_windows)
         shift = int(wlen) - int(params.overlap_seconds * sr)
         n_mel = shift * (n_mw - 1) + int(wlen)
@@ -442,7 +473,7 @@ def main() -> None:
 
     # ---- CPU baseline: the oracle (reference algorithm as written) on a bounded sample ----
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline = run_cpu_baseline(weights, st, audio, sr, int(wlen), args.beam, args.max_depth, args.geometry,
                                         args.model)
 
@@ -452,7 +483,7 @@ def main() -> None:
     # -- a third of the greedy run's decode work (round 4's leg).  The leg therefore runs the parity workload `tiny_beam5`
     # (tests/workloads.py: the same recipe WITHOUT the EOT ramp): every window runs beam 5 to depth 100.  `value` stays greedy.
     beam5 = None
-    if args.beam5_leg == "on" or (args.beam5_leg == "auto" and args.beam == 1 and args.geometry == "reference"):
+    if args.full and (args.beam5_leg == "on" or (args.beam5_leg == "auto" and args.beam == 1 and args.geometry == "reference")):
         bweights = synth.synth_preset(args.model, eot_beta=0.0)
         beng = wb.Whisper.from_tensors(bweights, device=local_rank)
         del bweights
@@ -509,8 +540,8 @@ def main() -> None:
 
     # ---- large-v2 leg (BASELINE.json's multi-GPU headline config): every rank decodes --large-v2-seconds of audio ----
     large_v2 = None
-    if args.large_v2_leg == "on" or (args.large_v2_leg == "auto" and args.model in ("tiny.en", "tiny_en")
-                                     and args.geometry == "reference" and args.beam == 1):
+    if args.full and (args.large_v2_leg == "on" or (args.large_v2_leg == "auto" and args.model in ("tiny.en", "tiny_en")
+                                                    and args.geometry == "reference" and args.beam == 1)):
         eng.close()
         del pcm_dev
         # (checkpoint without the <|endoftext|> ramp: every window decodes max_depth tokens -- the leg's work does not depend
@@ -642,35 +673,38 @@ def main() -> None:
 
     if rank == 0:
         audio_s = args.seconds * world * args.steps
-        lo, hi = shard.partition_windows(n_win, rank, world)
-        gen_lens = [max(0, len(r) - 4) for r in per_window[lo:hi]] if args.beam == 1 else None
-        # (split-precision encoder: its MFMA peak is a third of the fp16 dense peak -- three instructions per product)
-        enc_peak = enc_gemm if enc_gemm == "f16x3" else args.dtype
-        rl = e2e_roofline_ms(eng.dims, lens[lo:hi], 3 + args.max_depth, args.dtype,
-                             eng.max_mel_frames() - params.padding, gen_lens=gen_lens, encoder_peak=enc_peak)   # per rank (weak scaling)
-        work = rl.pop("_work")
-        if stages:
-            # achieved rates of the two big stages from their algorithmic work: encoder + cross-K/V from the profiled
-            # passes (large kernels, launch mode does not matter), decode from the TIMED steps minus those stages
-            enc_ms = stages["encoder_ms_per_step"] + stages["cross_kv_ms_per_step"]
-            dec_ms = dt / args.steps * 1e3 - enc_ms - stages["mel_ms_per_step"]
-            stages["encoder_TFLOPs_algorithmic"] = round(work["encoder_flops"] / (enc_ms * 1e-3) / 1e12, 2) if enc_ms > 0 else None
-            stages["encoder_frac_of_mfma_peak"] = round(work["encoder_flops"] / (enc_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[enc_peak], 4) if enc_ms > 0 else None
-            stages["decode_GBps_algorithmic"] = round(work["decode_bytes"] / (dec_ms * 1e-3) / 1e9, 1) if dec_ms > 0 else None
-            stages["decode_frac_of_hbm_peak"] = round(work["decode_bytes"] / (dec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dec_ms > 0 else None
         rtf = audio_s / dt
-        hstandard = args.model in ("tiny.en", "tiny_en") and args.seconds == 30.0 and args.max_depth == 100 and args.beam == 1
-        hcheck = check_against_golden(per_window, "tiny_bench" if args.geometry == "reference" else "tiny_whisper30", world) \
-            if hstandard else {"tokens_checked": None, "why": "no committed golden for this non-default workload"}
-        rl_rtf = args.seconds / (rl["total"] * 1e-3)
-        e2e = {"roofline_rtf": round(rl_rtf, 1), "frac": round((rtf / world) / rl_rtf, 4),
-               "roofline_ms_per_step": {k: round(v, 4) for k, v in rl.items()},
-               "generated_tokens_per_window": gen_lens,
-               "note": "per-GPU roofline of the same step: algorithmic bytes over 8 TB/s (mel, decode) and FLOPs over "
-                       "the dense MFMA peak of the path's dtype (encoder, cross-K/V); decode bytes are the NECESSARY ones "
-                       "(weights once per step while any window is live, a window's cached K/V only while it is live); "
-                       "decode is latency-bound at this size: the whole decode of a window batch is ONE persistent launch "
-                       "(stages.decode_launches_per_step) whose 12 dependent roles per token hand planes over between CUs"}
+        e2e = None
+        hcheck = {"tokens_checked": None, "why": "plain run: the comparison with the committed oracle rows runs with --full"}
+        if args.full:
+            lo, hi = shard.partition_windows(n_win, rank, world)
+            gen_lens = [max(0, len(r) - 4) for r in per_window[lo:hi]] if args.beam == 1 else None
+            # (split-precision encoder: its MFMA peak is a third of the fp16 dense peak -- three instructions per product)
+            enc_peak = enc_gemm if enc_gemm == "f16x3" else args.dtype
+            rl = e2e_roofline_ms(eng.dims, lens[lo:hi], 3 + args.max_depth, args.dtype,
+                                 eng.max_mel_frames() - params.padding, gen_lens=gen_lens, encoder_peak=enc_peak)   # per rank (weak scaling)
+            work = rl.pop("_work")
+            if stages:
+                # achieved rates of the two big stages from their algorithmic work: encoder + cross-K/V from the profiled
+                # passes (large kernels, launch mode does not matter), decode from the TIMED steps minus those stages
+                enc_ms = stages["encoder_ms_per_step"] + stages["cross_kv_ms_per_step"]
+                dec_ms = dt / args.steps * 1e3 - enc_ms - stages["mel_ms_per_step"]
+                stages["encoder_TFLOPs_algorithmic"] = round(work["encoder_flops"] / (enc_ms * 1e-3) / 1e12, 2) if enc_ms > 0 else None
+                stages["encoder_frac_of_mfma_peak"] = round(work["encoder_flops"] / (enc_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[enc_peak], 4) if enc_ms > 0 else None
+                stages["decode_GBps_algorithmic"] = round(work["decode_bytes"] / (dec_ms * 1e-3) / 1e9, 1) if dec_ms > 0 else None
+                stages["decode_frac_of_hbm_peak"] = round(work["decode_bytes"] / (dec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dec_ms > 0 else None
+            hstandard = args.model in ("tiny.en", "tiny_en") and args.seconds == 30.0 and args.max_depth == 100 and args.beam == 1
+            hcheck = check_against_golden(per_window, "tiny_bench" if args.geometry == "reference" else "tiny_whisper30", world) \
+                if hstandard else {"tokens_checked": None, "why": "no committed golden for this non-default workload"}
+            rl_rtf = args.seconds / (rl["total"] * 1e-3)
+            e2e = {"roofline_rtf": round(rl_rtf, 1), "frac": round((rtf / world) / rl_rtf, 4),
+                   "roofline_ms_per_step": {k: round(v, 4) for k, v in rl.items()},
+                   "generated_tokens_per_window": gen_lens,
+                   "note": "per-GPU roofline of the same step: algorithmic bytes over 8 TB/s (mel, decode) and FLOPs over "
+                           "the dense MFMA peak of the path's dtype (encoder, cross-K/V); decode bytes are the NECESSARY ones "
+                           "(weights once per step while any window is live, a window's cached K/V only while it is live); "
+                           "decode is latency-bound at this size: the whole decode of a window batch is ONE persistent launch "
+                           "(stages.decode_launches_per_step) whose 12 dependent roles per token hand planes over between CUs"}
         out = {
             "metric": "real-time factor (audio-sec/wall-sec)",
             "value": round(audio_s / dt, 2),

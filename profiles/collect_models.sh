@@ -10,10 +10,10 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 run() {   # name, bench args...
   local name=$1; shift
-  python "$R/bench.py" "$@" --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_$name.log" 2>&1
+  python "$R/bench.py" "$@" --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_$name.log" 2>&1
   grep '^{"metric' "$OUT/bench_$name.log" > "$OUT/bench_$name.json"
   rm -rf /tmp/p_$name
-  rocprofv3 --kernel-trace --stats -d /tmp/p_$name -o kt -- python "$R/bench.py" "$@" --steps 1 --warmup 1 --no-cpu-baseline \
+  rocprofv3 --kernel-trace --stats -d "$TMPDIR/p_$name" -o kt -- python "$R/bench.py" "$@" --full --steps 1 --warmup 1 --no-cpu-baseline \
     > "$OUT/stats_$name.log" 2>&1
   python "$R/profiles/summarize_rocprof.py" "$(find /tmp/p_$name -name '*.db' | head -1)" "$OUT/kernel_stats_$name.csv"
 }

@@ -8,6 +8,7 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -64,9 +65,12 @@ def _run(emu_lib, which, extra_env=None, allow=True):
     return fut.result() if fut is not None else _spawn(emu_lib, which, extra_env, allow)
 
 
+_STAMPS_DIR = tempfile.mkdtemp(prefix="ps_stamps_")      # this session's own: a shared temp dir may hold other users' files
+
+
 def _stamps_path(which, env):
     tag = "_".join([which] + [f"{k[-6:]}{v}" for k, v in sorted(env.items())])
-    return os.path.join(os.environ.get("TMPDIR", "/tmp"), f"ps_stamps_test_{tag}.bin")
+    return os.path.join(_STAMPS_DIR, f"ps_stamps_test_{tag}.bin")
 
 
 def _persist_env(which, env):
@@ -297,7 +301,7 @@ def test_bench_main_runs_to_its_json_line(emu_lib, extra):
     import json
     env = dict(os.environ)
     env["WHISPER_HIP_LIB"] = emu_lib
-    p = subprocess.run([sys.executable, os.path.join(PKG, "tools", "bench_dry_run.py"), "--steps", "1", "--warmup", "0",
+    p = subprocess.run([sys.executable, os.path.join(PKG, "tools", "bench_dry_run.py"), "--full", "--steps", "1", "--warmup", "0",
                         "--mel-windows", "2", "--seconds", "4", "--max-depth", "4"] + extra, env=env, capture_output=True,
                        text=True, timeout=600)
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
@@ -340,7 +344,7 @@ def test_bench_main_two_ranks_over_gloo(emu_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["WHISPER_HIP_LIB"] = emu_lib
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(port), os.path.join(PKG, "tools", "bench_dry_run.py"), "--gpus", "2",
+                        "127.0.0.1", "--master-port", str(port), os.path.join(PKG, "tools", "bench_dry_run.py"), "--full", "--gpus", "2",
                         "--steps", "1", "--warmup", "0", "--mel-windows", "2", "--seconds", "8", "--max-depth", "4",
                         "--large-v2-seconds", "8", "--beam5-leg", "off"],
                        env=env, capture_output=True, text=True, timeout=900)
@@ -358,6 +362,41 @@ def test_bench_main_two_ranks_over_gloo(emu_lib):
     ro = out["config"]["ranks_observed"]
     assert ro["world_size"] == 2 and ro["backend"] == "gloo" and [r[0] for r in ro["rank_local_rank_device"]] == [0, 1]
     assert out["config"]["tokens_checked"] is None and lv["config"]["tokens_checked"] is None
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(emu_lib, tmp_path):
+    """Without --full the bench line carries the headline figure and nothing else is run (no extra leg, profiled pass,
+    CPU baseline or golden comparison); --steps sets the timed steps; --dump-outputs writes the last timed step's token
+    ids, and two runs with the same arguments write the same arrays (seeded inputs)."""
+    import json
+
+    import numpy as np
+    env = dict(os.environ)
+    env["WHISPER_HIP_LIB"] = emu_lib
+    outs, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(PKG, "tools", "bench_dry_run.py"), "--steps", "2", "--warmup", "1",
+                            "--seconds", "4", "--max-depth", "4", "--dump-outputs", str(d)], env=env, capture_output=True,
+                           text=True, timeout=600)
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+        assert p.returncode == 0 and len(lines) == 1, p.stdout[-1500:] + p.stderr[-3000:]
+        outs.append(json.loads(lines[0]))
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("tokens", "window_tokens", "window_lens")})
+    out = outs[0]
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "x real-time" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - 4.0 / (out["ms_per_step"] * 1e-3)) < 0.05 * out["value"]
+    for leg in ("roofline", "kernels", "cpu_baseline", "e2e_roofline", "from_host_pcm", "mel_frontend", "stages", "beam5",
+                "large_v2"):
+        assert out[leg] is None, leg
+    assert out["config"]["tokens_checked"] is None
+    a, b = dumps
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["window_lens"].shape == (out["config"]["windows"],) and a["tokens"].size == out["config"]["tokens_out"]
+    for i, n in enumerate(a["window_lens"].astype(int)):
+        assert n >= 4 and (a["window_tokens"][i, :n] >= 0).all() and (a["window_tokens"][i, n:] == -1).all()
+    assert all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def test_outputs_are_bitwise_independent_of_the_schedule(emu_lib):
