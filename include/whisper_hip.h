@@ -106,6 +106,20 @@ int wb_model_set_ln_variant(wb_model* m, int eps_inside_sqrt);
  *                            formulas (transcribe.rs:32-34, :171-177) with the larger bound. */
 int wb_model_set_frame_limit(wb_model* m, int whisper_geometry);
 
+/* Log-mel frontend of every PCM entry point of this model (wb_session_begin, wb_waveform_to_tokens and its _prompted /
+ * _dev / _sharded forms):
+ *   0 = WB_FRONTEND_FFT        K1: 20x20 FFT with exact twiddles -- closer to the true log-mel than the
+ *                              reference                                                              [default]
+ *   1 = WB_FRONTEND_REFERENCE  the reference's own recipe (stfft, audio.rs:284-367): a dense f32 DFT against its f32
+ *                              angle table b[k][n] = f32(f32(k) * f32(2 pi / 400)) * f32(n) on exact-f32 MFMA, the
+ *                              log10 as ln(x) / f32(ln 10) and the clamp as relu(x - m8) + m8 on every element
+ *                              (audio.rs:34-56, helper.rs:8-27): what the reference computes, to ~1e-5 on every bin.
+ * Any other value -> WB_ERR_ARG (the mode is unchanged).  A session takes the mode at wb_session_begin. */
+enum { WB_FRONTEND_FFT = 0, WB_FRONTEND_REFERENCE = 1 };
+int wb_model_set_frontend(wb_model* m, int frontend);
+/* The current mode (0 / 1), WB_ERR_ARG for a null model. */
+int wb_model_frontend(const wb_model* m);
+
 /* Arithmetic of the encoder-side Linear layers of this model (chosen at load time; 1 can turn into 0 ONCE, see below):
  *   0 = exact-f32 MFMA (v_mfma_f32_32x32x2_f32)
  *   1 = split precision: three fp16 MFMAs per product on fp16 hi / lo pieces, f32 accumulation -- f32-grade results
@@ -133,6 +147,10 @@ int64_t wb_max_waveform_samples(int64_t n_frame_max);
  * (audio.rs:292 assert). */
 int wb_prep_audio(int device, const float* pcm, int64_t n, double sample_rate, float* mel,
                   int64_t* n_frames);
+/* The same with the frontend chosen per call (WB_FRONTEND_FFT = wb_prep_audio, WB_FRONTEND_REFERENCE; see
+ * wb_model_set_frontend); any other value -> WB_ERR_ARG. */
+int wb_prep_audio_frontend(int device, const float* pcm, int64_t n, double sample_rate, float* mel,
+                           int64_t* n_frames, int frontend);
 
 /* ---- WAV ingest with the reference's sample scaling (next to the hot path) ---------- */
 
@@ -175,6 +193,12 @@ int wb_waveform_to_mels_dev(int device, const float* pcm_dev, int64_t n_samples,
                             const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
                             int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
                             int32_t* frames_out, int32_t iters, double* elapsed_ms);
+/* The same with the frontend chosen per call (WB_FRONTEND_FFT = wb_waveform_to_mels_dev, WB_FRONTEND_REFERENCE); any
+ * other value -> WB_ERR_ARG.  Serves the batched reference-recipe frontend and its mel-frames/s measurement. */
+int wb_waveform_to_mels_dev_frontend(int device, const float* pcm_dev, int64_t n_samples, double sample_rate,
+                                     const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
+                                     int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
+                                     int32_t* frames_out, int32_t iters, double* elapsed_ms, int32_t frontend);
 
 /* Whisper::forward_encoder(mel [B,80,T]) -> [B,C,d], C=(T-1)/2+1, src/model/mod.rs:52-54,
  * :228-260.  T > n_audio_ctx -> WB_ERR_SHAPE (mod.rs:236-241). */
@@ -366,6 +390,12 @@ int wb_find_repeated_tokens_index(const int32_t* tokens, int64_t n, int64_t wind
  * (hann_window_device, audio.rs:272-278) and the dense [80][201] Slaney filterbank (get_mel_filters_device,
  * audio.rs:67-143; the kernel keeps it sparse).  No GPU needed; for table-vs-oracle tests. */
 int wb_mel_constants(double sample_rate, float* hann400, float* filters_80x201);
+
+/* The dense DFT table of the reference-recipe frontend (WB_FRONTEND_REFERENCE), built on the host as the kernel uses it
+ * (before its padding to 416 rows): [402][400], row 2k = cos(b[k][n]) * w[n], row 2k+1 = sin(b[k][n]) * (-w[n]) for
+ * bin k < 201 (audio.rs:348-364), b[k][n] = f32(f32(k) * f32(2 pi / 400)) * f32(n), cos / sin of that f32 angle
+ * correctly rounded to f32, w the Hann window of wb_mel_constants.  No GPU needed. */
+int wb_mel_dft_table(float* table_402x400);
 
 /* ---- measurement hooks ----------------------------------------------------------- */
 

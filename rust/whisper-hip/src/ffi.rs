@@ -59,6 +59,8 @@ pub const WB_ERR_OOM: c_int = -5;
 pub const WB_ERR_STATE: c_int = -6;
 pub const WB_F32: c_int = 0;
 pub const WB_BF16: c_int = 1; // retired: wb_model_load_* return an error
+pub const WB_FRONTEND_FFT: c_int = 0;
+pub const WB_FRONTEND_REFERENCE: c_int = 1;
 
 extern "C" {
     pub fn wb_model_load_dump_dir(dir: *const c_char, device: c_int, compute_dtype: c_int, out: *mut *mut wb_model) -> c_int;
@@ -67,11 +69,16 @@ extern "C" {
     pub fn wb_model_dims(m: *const wb_model, out: *mut wb_dims) -> c_int;
     pub fn wb_model_free(m: *mut wb_model);
     pub fn wb_model_set_frame_limit(m: *mut wb_model, whisper_geometry: c_int) -> c_int;
+    pub fn wb_model_set_frontend(m: *mut wb_model, frontend: c_int) -> c_int;
+    pub fn wb_model_frontend(m: *const wb_model) -> c_int;
     pub fn wb_model_encoder_gemm(m: *const wb_model) -> c_int;
     pub fn wb_model_decoder_gemm(m: *const wb_model) -> c_int;
     pub fn wb_max_waveform_samples(n_frame_max: i64) -> i64;
     pub fn wb_prep_audio(device: c_int, pcm: *const c_float, n: i64, sample_rate: c_double, mel: *mut c_float,
                          n_frames: *mut i64) -> c_int;
+    pub fn wb_prep_audio_frontend(device: c_int, pcm: *const c_float, n: i64, sample_rate: c_double, mel: *mut c_float,
+                                  n_frames: *mut i64, frontend: c_int) -> c_int;
+    pub fn wb_mel_dft_table(table_402x400: *mut c_float) -> c_int;
     pub fn wb_forward_encoder(m: *mut wb_model, mel: *const c_float, b: c_int, t: c_int, out: *mut c_float) -> c_int;
     pub fn wb_forward_decoder(m: *mut wb_model, tokens: *const i32, n: c_int, l: c_int, enc: *const c_float, c: c_int,
                               logits: *mut c_float) -> c_int;

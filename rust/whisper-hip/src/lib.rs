@@ -118,6 +118,13 @@ impl Whisper {
     pub fn set_frame_limit(&mut self, whisper_geometry: bool) -> Result<()> {
         check(unsafe { ffi::wb_model_set_frame_limit(self.raw, whisper_geometry as c_int) })
     }
+    /// Log-mel frontend of every PCM entry point: 0 = K1's exact-twiddle FFT (default), 1 = the reference's own recipe
+    /// (`stfft`, audio.rs:284-367: dense f32 DFT against its f32 angle table); anything else is an error.
+    pub fn set_frontend(&mut self, frontend: i32) -> Result<()> {
+        check(unsafe { ffi::wb_model_set_frontend(self.raw, frontend as c_int) })
+    }
+    /// The current log-mel frontend (0 / 1).
+    pub fn frontend(&self) -> i32 { unsafe { ffi::wb_model_frontend(self.raw) as i32 } }
 
     /// Arithmetic of the encoder-side Linear layers: 0 = exact-f32 MFMA, 1 = split precision (three fp16 MFMAs per
     /// product, f32-grade; the default).

@@ -109,6 +109,19 @@ int wb_model_set_frame_limit(wb_model* m, int whisper_geometry) {
   return WB_OK;
 }
 
+int wb_model_set_frontend(wb_model* m, int frontend) {
+  WB_REQUIRE(m, WB_ERR_ARG, "wb_model_set_frontend: null model");
+  WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
+             "wb_model_set_frontend: frontend %d is neither 0 (FFT) nor 1 (reference recipe)", frontend);
+  __atomic_store_n(&m->frontend, frontend, __ATOMIC_RELAXED);
+  return WB_OK;
+}
+
+int wb_model_frontend(const wb_model* m) {
+  if (!m) return WB_ERR_ARG;
+  return __atomic_load_n(&m->frontend, __ATOMIC_RELAXED);
+}
+
 int wb_model_encoder_gemm(const wb_model* m) {
   if (!m) return WB_ERR_ARG;
   return m->split_active() ? 1 : 0;        // (0 as well once the range guard of the split kernel has tripped)
@@ -140,19 +153,35 @@ int wb_mel_constants(double sample_rate, float* hann400, float* filters_80x201) 
   return WB_OK;
 }
 
+int wb_mel_dft_table(float* table_402x400) {
+  // host only: the reference recipe's DFT operand (audio.rs:348-364) as mel_dft.hip uses it, before padding
+  WB_REQUIRE(table_402x400, WB_ERR_ARG, "wb_mel_dft_table: null argument");
+  auto t = std::make_unique<MelTables>();
+  WB_REQUIRE(mel_tables_build(16000.0, t.get()) == 0, WB_ERR_SHAPE, "mel tables");
+  mel_dft_table_build(t->hann, table_402x400);
+  return WB_OK;
+}
+
 int64_t wb_max_waveform_samples(int64_t n_frame_max) {
   // audio.rs:12-17 with N_FFT = 400 (even)
   return MEL_HOP * (n_frame_max + 1) + (MEL_N_FFT % 2) - 1;
 }
 
 int wb_prep_audio(int device, const float* pcm, int64_t n, double sample_rate, float* mel, int64_t* n_frames) {
+  return wb_prep_audio_frontend(device, pcm, n, sample_rate, mel, n_frames, WB_FRONTEND_FFT);
+}
+
+int wb_prep_audio_frontend(int device, const float* pcm, int64_t n, double sample_rate, float* mel, int64_t* n_frames,
+                           int frontend) {
   WB_REQUIRE(pcm && mel, WB_ERR_ARG, "wb_prep_audio: null argument");
+  WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
+             "wb_prep_audio: frontend %d is neither 0 (FFT) nor 1 (reference recipe)", frontend);
   WB_REQUIRE(n >= MEL_N_FFT, WB_ERR_SHAPE, "prep_audio: %lld samples < n_fft = 400 (audio.rs:292)", (long long)n);
   WB_REQUIRE(n < ((int64_t)1 << 31), WB_ERR_SHAPE, "prep_audio: window too long");
   wb::GpuTurn turn(device);
   WB_HIP(hipSetDevice(device));
-  const MelTables* tabs;
-  WB_TRY(get_mel_tables(device, sample_rate, &tabs));
+  MelFrontend fe;
+  WB_TRY(get_mel_frontend(device, sample_rate, frontend, &fe));
   const int T = (int)(n / MEL_HOP);
   DevMem d_pcm, d_out, d_win, d_max;
   WB_TRY(d_pcm.alloc((size_t)n * 4));
@@ -163,9 +192,8 @@ int wb_prep_audio(int device, const float* pcm, int64_t n, double sample_rate, f
   hipStream_t st = nullptr;
   WB_HIP(hipMemcpyAsync(d_pcm.p, pcm, (size_t)n * 4, hipMemcpyHostToDevice, st));
   WB_HIP(hipMemcpyAsync(d_win.p, &w, sizeof(w), hipMemcpyHostToDevice, st));
-  launch_mel_spectrogram(st, d_pcm.as<float>(), d_win.as<MelWindow>(), 1, T, tabs, d_out.as<float>(),
-                         (int64_t)80 * T, T, d_max.as<float>(), 0, T);
-  launch_mel_finalize(st, d_win.as<MelWindow>(), 1, d_out.as<float>(), (int64_t)80 * T, T, d_max.as<float>(), T);
+  launch_mel_frontend(st, fe, d_pcm.as<float>(), d_win.as<MelWindow>(), 1, T, d_out.as<float>(), (int64_t)80 * T, T,
+                      d_max.as<float>(), 0, T);
   WB_HIP(hipGetLastError());
   WB_HIP(hipMemcpyAsync(mel, d_out.p, (size_t)80 * T * 4, hipMemcpyDeviceToHost, st));
   WB_HIP(hipStreamSynchronize(st));
@@ -177,7 +205,18 @@ int wb_waveform_to_mels_dev(int device, const float* pcm_dev, int64_t n_samples,
                             const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
                             int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
                             int32_t* frames_out, int32_t iters, double* elapsed_ms) {
+  return wb_waveform_to_mels_dev_frontend(device, pcm_dev, n_samples, sample_rate, starts, lens, n_windows, clip_frames,
+                                          padding, mel_dev, win_stride, row_stride, frames_out, iters, elapsed_ms,
+                                          WB_FRONTEND_FFT);
+}
+
+int wb_waveform_to_mels_dev_frontend(int device, const float* pcm_dev, int64_t n_samples, double sample_rate,
+                                     const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
+                                     int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
+                                     int32_t* frames_out, int32_t iters, double* elapsed_ms, int32_t frontend) {
   WB_REQUIRE(pcm_dev && starts && lens && mel_dev && n_windows > 0, WB_ERR_ARG, "wb_waveform_to_mels_dev: bad argument");
+  WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
+             "wb_waveform_to_mels_dev: frontend %d is neither 0 (FFT) nor 1 (reference recipe)", frontend);
   WB_REQUIRE(clip_frames > 0 && padding >= 0 && iters >= 1, WB_ERR_ARG, "wb_waveform_to_mels_dev: bad clip/padding/iters");
   std::vector<MelWindow> wins(n_windows);
   int maxF = 0, maxT = 0;
@@ -198,8 +237,8 @@ int wb_waveform_to_mels_dev(int device, const float* pcm_dev, int64_t n_samples,
              "wb_waveform_to_mels_dev: row_stride %d must be a multiple of 4 and >= %d frames", row_stride, maxT);
   wb::GpuTurn turn(device);
   WB_HIP(hipSetDevice(device));
-  const MelTables* tabs;
-  WB_TRY(get_mel_tables(device, sample_rate, &tabs));
+  MelFrontend fe;
+  WB_TRY(get_mel_frontend(device, sample_rate, frontend, &fe));
   DevMem d_win, d_max;
   WB_TRY(d_win.alloc(wins.size() * sizeof(MelWindow)));
   WB_TRY(d_max.alloc((size_t)n_windows * mel_bmax_stride(maxF) * 2 * 4));
@@ -212,9 +251,8 @@ int wb_waveform_to_mels_dev(int device, const float* pcm_dev, int64_t n_samples,
   hipEvent_t& e0 = ev.a; hipEvent_t& e1 = ev.b;
   if (elapsed_ms) { WB_HIP(hipEventCreate(&e0)); WB_HIP(hipEventCreate(&e1)); WB_HIP(hipEventRecord(e0, st)); }
   for (int it = 0; it < iters; it++) {
-    launch_mel_spectrogram(st, pcm_dev, d_win.as<MelWindow>(), n_windows, maxF, tabs, mel_dev, win_stride, row_stride,
-                           d_max.as<float>(), padding, row_stride);
-    launch_mel_finalize(st, d_win.as<MelWindow>(), n_windows, mel_dev, win_stride, row_stride, d_max.as<float>(), maxF);
+    launch_mel_frontend(st, fe, pcm_dev, d_win.as<MelWindow>(), n_windows, maxF, mel_dev, win_stride, row_stride,
+                        d_max.as<float>(), padding, row_stride);
   }
   if (elapsed_ms) WB_HIP(hipEventRecord(e1, st));
   WB_HIP(hipGetLastError());

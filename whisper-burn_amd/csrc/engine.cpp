@@ -45,6 +45,62 @@ int get_mel_tables(int device, double sample_rate, const MelTables** out_dev) {
   return WB_OK;
 }
 
+// The reference recipe's DFT table, transposed to [400][MEL_DFT_ROWS_PAD] (666 KB), once per device.
+static int get_mel_dft_table(int device, const float** out_dev) {
+  static std::mutex mu;
+  static std::map<int, float*> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(device);
+  if (it != cache.end()) { *out_dev = it->second; return WB_OK; }
+  auto tabs = std::make_unique<MelTables>();
+  WB_REQUIRE(mel_tables_build(16000.0, tabs.get()) == 0, WB_ERR_SHAPE, "mel tables");   // (the Hann window only)
+  std::vector<float> t((size_t)MEL_DFT_ROWS * MEL_N_FFT), tt((size_t)MEL_N_FFT * MEL_DFT_ROWS_PAD, 0.f);
+  mel_dft_table_build(tabs->hann, t.data());
+  for (int r = 0; r < MEL_DFT_ROWS; r++)
+    for (int n = 0; n < MEL_N_FFT; n++) tt[(size_t)n * MEL_DFT_ROWS_PAD + r] = t[(size_t)r * MEL_N_FFT + n];
+  float* dev = nullptr;
+  WB_HIP(hipSetDevice(device));
+  WB_HIP(hipMalloc(&dev, tt.size() * 4));
+  {  // (as get_mel_tables: a stream of its own)
+    hipStream_t ts = nullptr;
+    WB_HIP(hipStreamCreateWithFlags(&ts, hipStreamNonBlocking));
+    const hipError_t e1 = hipMemcpyAsync(dev, tt.data(), tt.size() * 4, hipMemcpyHostToDevice, ts);
+    const hipError_t e2 = hipStreamSynchronize(ts);
+    (void)hipStreamDestroy(ts);
+    WB_HIP(e1);
+    WB_HIP(e2);
+  }
+  cache[device] = dev;
+  *out_dev = dev;
+  return WB_OK;
+}
+
+int get_mel_frontend(int device, double sample_rate, int frontend, MelFrontend* out) {
+  WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
+             "log-mel frontend %d: 0 (FFT) or 1 (reference recipe)", frontend);
+  out->frontend = frontend;
+  WB_TRY(get_mel_tables(device, sample_rate, &out->tabs));
+  out->dft_tab = nullptr;
+  if (frontend == WB_FRONTEND_REFERENCE) WB_TRY(get_mel_dft_table(device, &out->dft_tab));
+  return WB_OK;
+}
+
+void launch_mel_frontend(hipStream_t st, const MelFrontend& fe, const float* pcm, const MelWindow* wins_dev, int n_windows,
+                         int max_frames, float* out, int64_t win_stride, int row_stride, float* bmax_dev, int pad,
+                         int pad_limit, const std::function<void()>& between) {
+  if (fe.frontend == WB_FRONTEND_REFERENCE) {
+    launch_mel_dft(st, pcm, wins_dev, n_windows, max_frames, fe.tabs, fe.dft_tab, out, win_stride, row_stride, bmax_dev,
+                   pad, pad_limit);
+    if (between) between();
+    launch_mel_dft_finalize(st, wins_dev, n_windows, out, win_stride, row_stride, bmax_dev, max_frames);
+    return;
+  }
+  launch_mel_spectrogram(st, pcm, wins_dev, n_windows, max_frames, fe.tabs, out, win_stride, row_stride, bmax_dev, pad,
+                         pad_limit);
+  if (between) between();
+  launch_mel_finalize(st, wins_dev, n_windows, out, win_stride, row_stride, bmax_dev, max_frames);
+}
+
 // Developer tool (WHISPER_HIP_ENC_TRACE=<dir>): stream-ordered device copies of every stage of an encoder pass, written to
 // <dir>/enc_trace_<tid>.bin at the end of the pass (one extra synchronisation there, none inside) -- to find the first stage
 // whose result differs between two runs (tools/probe_threads_enc.py).

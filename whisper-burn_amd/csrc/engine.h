@@ -45,6 +45,19 @@ int gemm_dispatch(const wb_model* m, hipStream_t st, const GemmArgs& a, int ldwt
 
 // Process-wide mel constant tables for (device, sample_rate).
 int get_mel_tables(int device, double sample_rate, const MelTables** out_dev);
+
+// The log-mel frontend of one call: K1 (mel.hip, WB_FRONTEND_FFT) or the reference recipe (mel_dft.hip,
+// WB_FRONTEND_REFERENCE), with its device tables (cached per device).  Every PCM entry point launches through here.
+struct MelFrontend {
+  int frontend = WB_FRONTEND_FFT;
+  const MelTables* tabs = nullptr;
+  const float* dft_tab = nullptr;   // reference recipe only: [400][MEL_DFT_ROWS_PAD]
+};
+int get_mel_frontend(int device, double sample_rate, int frontend, MelFrontend* out);
+// main kernel + finalize; `between` (optional) runs after the main launch (developer trace stages)
+void launch_mel_frontend(hipStream_t st, const MelFrontend& fe, const float* pcm, const MelWindow* wins_dev, int n_windows,
+                         int max_frames, float* out, int64_t win_stride, int row_stride, float* bmax_dev, int pad,
+                         int pad_limit, const std::function<void()>& between = {});
 // developer tool (WHISPER_HIP_ENC_TRACE): a stream-ordered copy of one more stage into this thread's encoder trace
 void enc_trace_stage(hipStream_t st, const char* name, const void* p, size_t bytes);
 

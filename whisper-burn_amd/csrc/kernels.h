@@ -61,6 +61,18 @@ void launch_mel_spectrogram(hipStream_t st, const float* pcm, const MelWindow* w
 // clamp fix-up: max(x, gmax - 8) (audio.rs:52) on the tiles that need it (normally none: the log-mel is written once)
 void launch_mel_finalize(hipStream_t st, const MelWindow* wins_dev, int n_windows, float* out, int64_t win_stride,
                          int row_stride, const float* bmax_dev, int max_frames);
+// reference-recipe frontend (mel_dft.hip): dense f32 DFT on MFMA against the reference's own f32 angle table
+// (audio.rs:348-364); same window / output / bmax geometry as the two launches above, but the main kernel stores the
+// un-normalised log10 and the finalize applies relu(x - m8) + m8 and (x + 4) / 4 to every emitted element.
+constexpr int MEL_DFT_ROWS = 2 * MEL_N_BINS, MEL_DFT_ROWS_PAD = 416;   // Re / Im rows interleaved, padded to 13 x 32
+// host: table [402][400] (row 2k = cos(b[k]) * w, row 2k+1 = sin(b[k]) * (-w)) from the f32 Hann window
+void mel_dft_table_build(const float* hann400, float* table_402x400);
+// dft_tab_dev: the same table transposed and padded, [400][MEL_DFT_ROWS_PAD] (rows >= 402 zero)
+void launch_mel_dft(hipStream_t st, const float* pcm, const MelWindow* wins_dev, int n_windows, int max_frames,
+                    const MelTables* tabs_dev, const float* dft_tab_dev, float* out, int64_t win_stride, int row_stride,
+                    float* bmax_dev, int pad, int pad_limit);
+void launch_mel_dft_finalize(hipStream_t st, const MelWindow* wins_dev, int n_windows, float* out, int64_t win_stride,
+                             int row_stride, const float* bmax_dev, int max_frames);
 void launch_fill_f32(hipStream_t st, float* p, int64_t n, float v);
 // 16-bit PCM -> f32 with the reference's scale s / 32767 (bin/transcribe/main.rs:45-52), correctly rounded division
 void launch_pcm_s16_to_f32(hipStream_t st, const int16_t* src, int64_t n, float* dst);

@@ -256,8 +256,8 @@ int session_encode_pcm(wb_session* s, const float* pcm, int64_t n_pcm, const int
     maxF = std::max(maxF, nf); maxT = std::max(maxT, s->T[w]);
   }
   const int Ts = (maxT + 3) & ~3;
-  const MelTables* tabs;
-  WB_TRY(get_mel_tables(m->device, s->sample_rate, &tabs));
+  MelFrontend fe;
+  WB_TRY(get_mel_frontend(m->device, s->sample_rate, __atomic_load_n(&m->frontend, __ATOMIC_RELAXED), &fe));
   if (!pcm_on_device) WB_TRY(s->pcm.ensure((size_t)(hi - lo) * 4));
   WB_TRY(s->wins.ensure(wins.size() * sizeof(MelWindow)));
   WB_TRY(s->gmax.ensure((size_t)s->W * mel_bmax_stride(maxF) * 2 * 4));
@@ -291,12 +291,12 @@ int session_encode_pcm(wb_session* s, const float* pcm, int64_t n_pcm, const int
   if (!pcm_on_device && (trace_extra & 1)) enc_trace_stage(s->st, "pcm", s->pcm.p, (size_t)(hi - lo) * 4);
   {
     ScopedTimer tm(s->st, 0);
-    launch_mel_spectrogram(s->st, pcm_dev, s->wins.as<MelWindow>(), s->W, maxF, tabs, s->mel.as<float>(),
-                           (int64_t)80 * Ts, Ts, s->gmax.as<float>(), s->padding, Ts);
-    if (trace_extra & 2) enc_trace_stage(s->st, "mel0", s->mel.p, (size_t)s->W * 80 * Ts * 4);
-    if (trace_extra & 4) enc_trace_stage(s->st, "gmax", s->gmax.p, (size_t)s->W * mel_bmax_stride(maxF) * 2 * 4);
-    launch_mel_finalize(s->st, s->wins.as<MelWindow>(), s->W, s->mel.as<float>(), (int64_t)80 * Ts, Ts,
-                        s->gmax.as<float>(), maxF);
+    launch_mel_frontend(s->st, fe, pcm_dev, s->wins.as<MelWindow>(), s->W, maxF, s->mel.as<float>(), (int64_t)80 * Ts, Ts,
+                        s->gmax.as<float>(), s->padding, Ts, [&]() {
+                          if (trace_extra & 2) enc_trace_stage(s->st, "mel0", s->mel.p, (size_t)s->W * 80 * Ts * 4);
+                          if (trace_extra & 4)
+                            enc_trace_stage(s->st, "gmax", s->gmax.p, (size_t)s->W * mel_bmax_stride(maxF) * 2 * 4);
+                        });
     tm.stop();
     if (tm.on) { WB_HIP(hipStreamSynchronize(s->st)); tm.collect(); profile().ms[5] += 1; }
   }

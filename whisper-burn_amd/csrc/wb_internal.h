@@ -148,6 +148,9 @@ struct wb_model {
   // 1: ENCODER POSITIONS bounded by n_audio_ctx = 2 n_audio_ctx frames (Whisper's own 30 s geometry; opt-in)
   int frame_limit_x2 = 0;
   int max_mel_frames() const { return frame_limit_x2 ? 2 * dims.n_audio_ctx : dims.n_audio_ctx; }
+  // log-mel frontend of the PCM entry points (wb_model_set_frontend): WB_FRONTEND_FFT (K1) or WB_FRONTEND_REFERENCE;
+  // read once per encode (session_encode_pcm)
+  int frontend = WB_FRONTEND_FFT;
   // all weights live in one arena allocation
   wb::DevMem arena;
   wb::DevMem arena_split;     // exact-f32 models with the split-precision encoder: fp16 hi / lo copies of the encoder-side weights

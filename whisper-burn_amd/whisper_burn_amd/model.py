@@ -55,9 +55,29 @@ def max_waveform_samples(n_frame_max: int) -> int:
     return int(_lib.load().wb_max_waveform_samples(int(n_frame_max)))
 
 
-def prep_audio(waveform, sample_rate: float = 16000.0, device: int = 0) -> np.ndarray:
-    """audio.rs:34: waveform [n_batch, n_samples] -> log-mel [n_batch, 80, n_samples // 160]."""
+FRONTENDS = {"fft": 0, "reference": 1}
+
+
+def frontend_id(frontend: str) -> int:
+    """"fft" (K1, the default) -> 0, "reference" (the reference's dense f32 DFT recipe) -> 1."""
+    if frontend not in FRONTENDS:
+        raise ValueError(f"frontend {frontend!r}: one of {sorted(FRONTENDS)}")
+    return FRONTENDS[frontend]
+
+
+def mel_dft_table() -> np.ndarray:
+    """The [402, 400] DFT operand of the reference-recipe frontend (host only, no GPU): row 2k = cos(b[k]) * w,
+    row 2k+1 = sin(b[k]) * (-w), audio.rs:348-364."""
+    t = np.empty((402, 400), dtype=np.float32)
+    check(_lib.load().wb_mel_dft_table(_fp(t)))
+    return t
+
+
+def prep_audio(waveform, sample_rate: float = 16000.0, device: int = 0, frontend: str = "fft") -> np.ndarray:
+    """audio.rs:34: waveform [n_batch, n_samples] -> log-mel [n_batch, 80, n_samples // 160].
+    frontend="reference" computes the reference's own recipe (dense f32 DFT, wb_prep_audio_frontend)."""
     lib = _lib.load()
+    fid = frontend_id(frontend)
     w = _f32(waveform)
     if w.ndim == 1:
         w = w[None]
@@ -66,7 +86,7 @@ def prep_audio(waveform, sample_rate: float = 16000.0, device: int = 0) -> np.nd
         n = row.shape[0]
         mel = np.empty((80, max(n // 160, 0)), dtype=np.float32)
         nf = C.c_int64(0)
-        check(lib.wb_prep_audio(device, _fp(row), n, float(sample_rate), _fp(mel), C.byref(nf)))
+        check(lib.wb_prep_audio_frontend(device, _fp(row), n, float(sample_rate), _fp(mel), C.byref(nf), fid))
         out.append(mel)
     return np.stack(out)
 
@@ -140,18 +160,20 @@ def pcm_s16_to_f32_dev(src_ptr: int, n: int, dst_ptr: int, device: int = 0) -> N
 
 def waveform_to_mels_dev(pcm_ptr: int, n_samples: int, starts, lens, mel_ptr: int, win_stride: int, row_stride: int,
                          sample_rate: float = 16000.0, clip_frames: int = 1490, padding: int = 10, device: int = 0,
-                         iters: int = 1):
+                         iters: int = 1, frontend: str = "fft"):
     """transcribe.rs:114-138 + :171-177 for a batch of windows, device pointers in and out.
-    Returns (frames per window, HIP-event milliseconds of all `iters` passes)."""
+    Returns (frames per window, HIP-event milliseconds of all `iters` passes).  frontend: as `prep_audio`."""
+    fid = frontend_id(frontend)
     lib = _lib.load()
     st = np.ascontiguousarray(starts, dtype=np.int64)
     ln = np.ascontiguousarray(lens, dtype=np.int64)
     frames = np.zeros(len(st), dtype=np.int32)
     ms = C.c_double(0.0)
-    check(lib.wb_waveform_to_mels_dev(device, C.c_void_p(pcm_ptr), n_samples, float(sample_rate),
-                                      st.ctypes.data_as(_lib.c_int64_p), ln.ctypes.data_as(_lib.c_int64_p), len(st),
-                                      clip_frames, padding, C.c_void_p(mel_ptr), win_stride, row_stride,
-                                      frames.ctypes.data_as(_lib.c_int32_p), iters, C.byref(ms)))
+    check(lib.wb_waveform_to_mels_dev_frontend(device, C.c_void_p(pcm_ptr), n_samples, float(sample_rate),
+                                               st.ctypes.data_as(_lib.c_int64_p), ln.ctypes.data_as(_lib.c_int64_p),
+                                               len(st), clip_frames, padding, C.c_void_p(mel_ptr), win_stride,
+                                               row_stride, frames.ctypes.data_as(_lib.c_int32_p), iters, C.byref(ms),
+                                               fid))
     return frames, float(ms.value)
 
 
@@ -217,6 +239,19 @@ class Whisper:
         geometry" T = 3000, C = 1500 of SURVEY 8d config 2b); the reference panics on such a window."""
         check(_lib.load().wb_model_set_frame_limit(self._h, int(bool(whisper_geometry))))
         self._frame_limit_x2 = bool(whisper_geometry)
+
+    def set_frontend(self, name: str):
+        """Log-mel frontend of every PCM entry point of this model (wb_model_set_frontend): "fft" (K1, default) or
+        "reference" (the reference's own recipe, audio.rs:284-367: dense f32 DFT against its f32 angle table)."""
+        check(_lib.load().wb_model_set_frontend(self._h, frontend_id(name)))
+
+    @property
+    def frontend(self) -> str:
+        """The current log-mel frontend: "fft" or "reference"."""
+        v = _lib.load().wb_model_frontend(self._h)
+        if v < 0:
+            check(v)
+        return ("fft", "reference")[v]
 
     def encoder_gemm(self) -> str:
         """Arithmetic of the encoder-side Linear layers: "f32" (exact-f32 MFMA), "f16x3" (split precision: three fp16 MFMAs

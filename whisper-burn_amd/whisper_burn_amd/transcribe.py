@@ -6,6 +6,9 @@ directory (load.rs:295), the audio must be a 16 kHz mono WAV (main.rs:41-42; 16-
 hound does, :44-51), `tokenizer.json` is read from the working directory (token.rs:13-19), the transcript is
 written to `<transcription file>` (main.rs:151-154).  Exit code 1 with the reference's messages on bad input.
 
+`--frontend reference` after the four positional arguments computes the log-mel with the reference's own recipe
+(dense f32 DFT, wb_model_set_frontend) instead of the default exact-twiddle FFT.
+
 One addition: with `WHISPER_HIP_RESAMPLE=1` in the environment a mono WAV of another sample rate (the bundled
 22 050 Hz audio.wav, which the reference sends through `sox`, README.md:69-74) is resampled to 16 kHz on the GPU
 (wb_resample_dev) instead of being rejected.
@@ -26,6 +29,14 @@ def main(argv=None) -> int:
         print(f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file>", file=sys.stderr)
         return 1
     model_name, wav_file, lang, text_file = argv[1:5]
+    frontend = None
+    extra = argv[5:]
+    if extra and extra[0] == "--frontend":      # (other trailing arguments are ignored, as before)
+        if len(extra) < 2 or extra[1] not in ("fft", "reference"):
+            print(f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference]",
+                  file=sys.stderr)
+            return 1
+        frontend = extra[1]
     if lang not in LANGUAGES:
         print(f"Invalid language abbreviation: {lang}", file=sys.stderr)
         return 1
@@ -58,6 +69,8 @@ def main(argv=None) -> int:
     except Exception as e:                                                 # noqa: BLE001
         print(f"Failed to load whisper model file: {e}", file=sys.stderr)
         return 1
+    if frontend is not None:
+        whisper.set_frontend(frontend)
 
     class Bpe:                                                             # what waveform_to_text needs (transcribe.rs:23-29)
         def special_tokens(self, language):
