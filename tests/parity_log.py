@@ -46,6 +46,31 @@ def record(test: str, worst: float, tol: float, max_abs_logprob: float | None = 
     return rec
 
 
+RATIOS: dict = {}        # operator family -> {"worst": largest error / bound, "case": its case, "n": cases recorded}
+
+
+def record_ratio(family: str, case: str, ratio: float, **extra) -> None:
+    """Operator-level parity (tests/test_gpu_kernels.py): a case's worst |kernel - f64 reference| / bound.  The run's tail shows,
+    per operator family, the largest one -- how much headroom the kernels have under their bounds."""
+    e = RATIOS.setdefault(family, {"worst": -1.0, "case": None, "n": 0})
+    e["n"] += 1
+    if ratio > e["worst"]:
+        e["worst"], e["case"] = float(ratio), case
+    try:
+        with open(_path(), "a") as f:
+            f.write(json.dumps(dict(test=case, family=family, ratio=float(ratio), **extra)) + "\n")
+    except OSError:
+        pass
+
+
+def flush_ratios(**extra) -> None:
+    """One record per operator family (worst = the largest error / bound, tol = 1): the terminal summary prints them."""
+    for fam in sorted(RATIOS):
+        e = RATIOS[fam]
+        record(f"kernels/{fam}", e["worst"], 1.0, case=e["case"], n_cases=e["n"], **extra)
+    RATIOS.clear()
+
+
 def lines():
     for r in RECORDS:
         tail = "".join(f" {k}={r[k]:.3g}" if isinstance(r[k], float) else f" {k}={r[k]}"

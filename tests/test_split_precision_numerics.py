@@ -7,11 +7,7 @@ overflow, the three-product sum is as close to the exact product as an f32 GEMM,
 is why the pieces are fp16).  tests/study_split_precision.py measures the same thing through the whole model."""
 import numpy as np
 
-
-def split_f16(x):
-    hi = x.astype(np.float16).astype(np.float32)
-    lo = ((x - hi) * np.float32(2048.0)).astype(np.float16).astype(np.float32)
-    return hi, lo
+from kernel_refs import split_f16          # hi = fp16(x), lo = fp16((x - hi) 2^11): shared with the operator-level kernel tests
 
 
 def split_bf16(x):

@@ -371,6 +371,20 @@ __device__ __forceinline__ void a_split(float x, _Float16& hi, _Float16& lo) {
   hi = (_Float16)x;
   lo = (_Float16)((x - (float)hi) * A_LO_SCALE);
 }
+// The split of a PRODUCT (q * scale, k * scale).  Left visible to the compiler, the product was folded into the two uses of x in
+// a_split SEPARATELY: the stored hi became fp16(fl32(k s)) (v_cvt_pk_f16_f32 of the rounded product) while lo was taken against
+// fp16(k s) rounded ONCE from the exact product (v_fma_mixlo_f16 / v_fma_mix_f32) -- two different neighbours whenever fl32(k s)
+// lands on an fp16 tie, and the pair then reconstructs k s off by a whole fp16 ulp (2^-11 relative; found by
+// tests/test_gpu_kernels.py at scale != 1 -- the engine passes scale = 1, where there is no product to fold).  Both pieces must
+// come from ONE f32 value: the product is laundered through a register (no instruction), so neither use can see how it was made.
+#ifndef WB_LAUNDER_V                      // (the functional model tools/hipemu predefines the hook)
+#define WB_LAUNDER_V(x) asm volatile("" : "+v"(x))
+#endif
+__device__ __forceinline__ void a_split_scaled(float v, float scale, _Float16& hi, _Float16& lo) {
+  float x = v * scale;
+  WB_LAUNDER_V(x);
+  a_split(x, hi, lo);
+}
 __device__ __forceinline__ a_u16 a_bits(_Float16 h) { return __builtin_bit_cast(a_u16, h); }
 // slot position of tile key kv (0 .. 31) in a V^T row: see the header comment
 __device__ __forceinline__ int a_vslot(int kv) { return 16 * (kv >> 4) + 8 * ((kv >> 2) & 1) + (kv & 3) + 4 * ((kv >> 3) & 1); }
@@ -410,7 +424,7 @@ __global__ __launch_bounds__(NW * 64) void attention_f16x3_kernel(const float* _
       const float4 a = *reinterpret_cast<const float4*>(qp + 16 * ks), b = *reinterpret_cast<const float4*>(qp + 16 * ks + 4);
       const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
-      for (int i = 0; i < 8; i++) { _Float16 h, l; a_split(v[i] * scale, h, l); qh[ks][i] = h; ql[ks][i] = l; }
+      for (int i = 0; i < 8; i++) { _Float16 h, l; a_split_scaled(v[i], scale, h, l); qh[ks][i] = h; ql[ks][i] = l; }
     }
   }
 
@@ -439,14 +453,14 @@ __global__ __launch_bounds__(NW * 64) void attention_f16x3_kernel(const float* _
 #pragma unroll
     for (int i = 0; i < LD_PER_T; i++) {
       const int idx = tid + i * NTHR, r = idx >> 4, c4 = (idx & 15) * 4;
-      const float kv4[4] = {rk[i].x * scale, rk[i].y * scale, rk[i].z * scale, rk[i].w * scale};   // mod.rs:510-514
+      const float kv4[4] = {rk[i].x, rk[i].y, rk[i].z, rk[i].w};   // scaled below (mod.rs:510-514)
       const float vv4[4] = {rv[i].x, rv[i].y, rv[i].z, rv[i].w};
       a_u16 kh[4], kl[4];
       const int vs = a_vslot(r);
 #pragma unroll
       for (int c = 0; c < 4; c++) {
         _Float16 h, l;
-        a_split(kv4[c], h, l); kh[c] = a_bits(h); kl[c] = a_bits(l);
+        a_split_scaled(kv4[c], scale, h, l); kh[c] = a_bits(h); kl[c] = a_bits(l);
         a_split(vv4[c], h, l);
         Vth[buf][c4 + c][vs] = a_bits(h); Vtl[buf][c4 + c][vs] = a_bits(l);
       }
@@ -565,6 +579,7 @@ bool launch_attention(hipStream_t st, const float* Q, int ldq, const float* K, c
                       float scale, int causal, bool split, uint16_t* Oh, uint16_t* Ol) {
   if (n_segs <= 0 || max_q_len <= 0) return false;
   static const bool f16_enabled = [] { const char* e = getenv("WHISPER_HIP_ATTN_F16"); return !(e && e[0] == '0'); }();
+  // (tests/kernel_cases.py attn_branch mirrors this choice and the ladder of launch_attention_f32 below)
   const int64_t blocks128 = (int64_t)((max_q_len + 127) / 128) * n_head * n_segs;
   const bool kvsplit = !causal && max_q_len >= 256 && blocks128 < 384 && attention_kvsplit_enabled();
   if (split && f16_enabled && !kvsplit && max_q_len > 64) {

@@ -296,6 +296,8 @@ int launch_gemm_f32(hipStream_t st, const GemmArgs& a) {
   // the accumulation chain never changes).  Many-block shapes (>= 3 blocks per CU at 128x128) are fastest on
   // 128x128 tiles with two k-tiles in flight; everything smaller -- the bench's 3-window encoder, the N = d
   // projections of `small` -- on 32x128 tiles (1x4 waves), 32-deep k-tiles, two in flight.
+  // (tests/kernel_cases.py gemm_f32_branch mirrors this ladder and the conv1 one above to assert that the operator tests reach
+  // every branch: a retuned threshold must be retuned there too)
   if (a.ksplit > 1) {
     if (a.M <= 32) launch_cfg<32, 128, 1, 4, AMODE_ROWS, 32, 3>(st, a);
     else launch_cfg<64, 64, 2, 2, AMODE_ROWS, 32, 3>(st, a);

@@ -84,6 +84,9 @@ struct RowDesc {             // optional per-row A addressing (implicit-GEMM con
   int16_t klo, khi;          // A[m][k] := 0 for k outside [klo, khi)   (ROWS mode)
                              // CONV1 mode: klo = 1 if first frame of its window, khi = 1 if last
 };
+// Alignment: A rows are read as float4 -- A and every row start (m * lda, or desc[m].off) must be 16-byte aligned (lda % 4 == 0,
+// off % 4 == 0), and a row's whole quads around [klo, khi) must be readable (the elements outside the mask are discarded, not
+// used).  B is read as float4 along N up to ldb (ldb % 4 == 0, B 16-byte aligned): columns [N, ldb) are read and discarded.
 struct GemmArgs {
   const float* A = nullptr; int64_t lda = 0;     // ROWS: A[m][k] = A[m*lda + k] (or A[desc[m].off + k])
   const RowDesc* a_desc = nullptr;               // per-row descriptors (device), or null
@@ -119,6 +122,9 @@ void launch_split_weight_f16(hipStream_t st, const float* W, int K, int N, uint1
 
 // ---- elementwise / normalisation (ops.hip) ----------------------------------------
 // y[m] = LN(x[m]) * g + b, biased variance; eps placement per variant (see whisper_hip.h)
+// Contract (LayerNorm, its pieces variant and embed): rows are dense ([M][d]) and read / written as float4 -- d % 4 == 0 and
+// x, y, g, b (E, pos) 16-byte aligned, yh / yl 8-byte aligned.  The launchers do not check it: with d % 4 != 0 the tail of every
+// row would be dropped silently.  Every caller's d is a model width (a multiple of 64).
 void launch_layernorm(hipStream_t st, const float* x, float* y, int M, int d, const float* g, const float* b,
                       float eps, int eps_inside_sqrt);
 // ... with the result as fp16 pieces (GemmArgs::Ah / Al): yh, yl [M][d]
@@ -131,6 +137,9 @@ void launch_embed(hipStream_t st, const int32_t* tok, int n_rows, int L, int d, 
 // ---- attention (attention.hip) ---------------------------------------------------
 struct AttnSeg { int32_t q_row0, q_len, kv_row0, kv_len; };   // one (batch) segment of packed rows
 // O[q][h*64..] = softmax((Q*s)(K*s)^T [+causal]) V per segment and head, head size 64 (mod.rs:493-533)
+// causal: key kv is visible to query q iff kv <= q (positions inside the segment).  kv_len >= 1 for every segment with q_len > 0.
+// Contract: rows are read / written as float4 -- ldq % 4 == 0, ldkv % 4 == 0, ldo % 4 == 0 and Q, K, V, O 16-byte aligned
+// (Oh / Ol: 8-byte aligned); max_q_len >= every segment's q_len.  The launchers do not check it.
 void launch_attention_f32(hipStream_t st, const float* Q, int ldq, const float* K, const float* V, int ldkv,
                           float* O, int ldo, const AttnSeg* segs_dev, int n_segs, int max_q_len, int n_head,
                           float scale, int causal);

@@ -1,0 +1,343 @@
+// Test-only harness around the host-callable kernel launchers (csrc/kernels.h, csrc/decode.h): lib/libwhisper_hip_ktest.so.
+// NOT part of the product ABI (include/whisper_hip.h does not know it); tests/test_gpu_kernels.py and
+// tests/test_kernel_harness_emu.py drive it through ctypes.
+//
+// Every entry point takes HOST arrays, copies each one verbatim into a device allocation of the same size, calls ONE wb::launch_*
+// function of the already-built library, synchronises, and copies the output arrays back.  It contains no kernel.  The caller
+// hands in arrays that are LARGER than the contract (guard bands, padded leading dimensions, poisoned padding) together with the
+// byte offset at which the launcher's pointer starts inside the array; the harness verifies -- before any launch -- that
+// everything the contract lets the kernel touch lies inside those arrays and honours the alignment contracts of kernels.h.
+// A wrong kernel therefore shows up as a failed comparison in the test, not as a memory fault.
+//
+// Return value: the launcher's own status (0 / -1; void launchers: 0), WBK_EARG when the arguments fail the harness's checks
+// (nothing was launched), or -(1000 + hipError_t) for a HIP error.  Never aborts.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "decode.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int WBK_EARG = -2;
+
+struct Pool {                       // the device copies of one call
+  std::vector<void*> dev;
+  int err = 0;                      // first HIP error, as -(1000 + code)
+  ~Pool() { for (void* p : dev) (void)hipFree(p); }
+  bool ok(hipError_t e) { if (e != hipSuccess && err == 0) err = -(1000 + (int)e); return e == hipSuccess; }
+};
+
+extern "C" {
+// one host array: `bytes` long, the launcher's pointer starts `off` bytes into its device copy.  host == null: null pointer.
+struct WbkBuf { void* host; int64_t bytes; int64_t off; };
+}
+
+// device copy of b (verbatim); returns the base of the copy or null
+char* upload(Pool& P, const WbkBuf& b) {
+  if (!b.host || b.bytes <= 0) return nullptr;
+  void* d = nullptr;
+  if (!P.ok(hipMalloc(&d, (size_t)b.bytes))) return nullptr;
+  P.dev.push_back(d);
+  P.ok(hipMemcpy(d, b.host, (size_t)b.bytes, hipMemcpyHostToDevice));
+  return (char*)d;
+}
+void download(Pool& P, const WbkBuf& b, const char* d) {
+  if (d && b.host) P.ok(hipMemcpy(b.host, d, (size_t)b.bytes, hipMemcpyDeviceToHost));
+}
+// [lo, hi) in ELEMENTS of size esz relative to the launcher's pointer: inside the array?
+bool inside(const WbkBuf& b, int64_t lo, int64_t hi, int esz) {
+  if (!b.host) return false;
+  const int64_t blo = b.off + lo * esz, bhi = b.off + hi * esz;
+  return lo <= hi && blo >= 0 && bhi <= b.bytes;
+}
+bool aligned16(const WbkBuf& b, int64_t elem, int esz) { return ((b.off + elem * esz) & 15) == 0; }
+int finish(Pool& P, int status) {
+  P.ok(hipGetLastError());
+  P.ok(hipStreamSynchronize(nullptr));
+  return P.err ? P.err : status;
+}
+
+}  // namespace
+
+extern "C" {
+
+struct WbkGemm {
+  int64_t variant;                  // 0: launch_gemm_f32, 1: launch_gemm_f16x3 (weight split on the device from W)
+  WbkBuf A, Ah, Al, desc, B, W, Wh, Wl, C, Ch, Cl, bias, residual, aux, aux_idx;
+  int64_t residual_is_c;            // 1: residual = the C pointer itself (the aliasing the contract allows)
+  int64_t lda, a_mask_align, conv1_tstride, ldb, ldc, ldr, ld_aux, n_aux_rows;
+  int64_t col_scale_period, col_scale_width, M, N, K, act, ksplit, c_split_stride, c_block_cols, c_block_stride, ldwt;
+  int64_t use_range_flag, range_flag_out;
+  double col_scale;
+};
+
+// A, B, bias, residual, aux, aux_idx, desc, W: inputs.  C (or Ch / Cl), Wh / Wl: copied in AND back.
+int wbk_gemm(WbkGemm* g) {
+  const int64_t M = g->M, N = g->N, K = g->K;
+  if (M < 1 || N < 1 || K < 0 || M > (1 << 20) || N > (1 << 20) || K > (1 << 20)) return WBK_EARG;
+  const bool f16 = g->variant == 1, pre = g->Ah.host != nullptr, pieces_out = g->Ch.host != nullptr;
+  const bool conv1 = g->conv1_tstride > 0;
+  const int64_t Kc = (K + 31) / 32 * 32;                       // a refused K never reaches a kernel; the checks use the padded one
+  // ---- A ----
+  const wb::RowDesc* hd = (const wb::RowDesc*)g->desc.host;
+  if (hd && (g->desc.off != 0 || g->desc.bytes < M * (int64_t)sizeof(wb::RowDesc))) return WBK_EARG;
+  if (conv1) {
+    if (!hd || K % 3 != 0 || pre) return WBK_EARG;
+    for (int64_t m = 0; m < M; m++) {
+      const int64_t lo = hd[m].off - 1 + (hd[m].klo ? 1 : 0), hi = hd[m].off + (K / 3 - 1) * g->conv1_tstride + 2 - (hd[m].khi ? 1 : 0);
+      if (!inside(g->A, lo, hi, 4)) return WBK_EARG;
+    }
+  } else if (pre) {
+    if (!f16) return WBK_EARG;
+    // (Ah without Al is one of the launcher's own refusals: it returns before any launch, so Al's extent is moot)
+    if (g->Al.host && (g->Al.bytes != g->Ah.bytes || g->Al.off != g->Ah.off)) return WBK_EARG;
+    if (!inside(g->Ah, 0, (M - 1) * g->lda + Kc, 2) || (g->lda % 8 == 0 && !aligned16(g->Ah, 0, 2))) return WBK_EARG;
+  } else {
+    for (int64_t m = 0; m < M; m++) {
+      const int64_t start = hd ? hd[m].off : m * g->lda;
+      int64_t klo = hd ? hd[m].klo : 0, khi = hd ? hd[m].khi : Kc;
+      if (klo < 0 || khi > Kc) return WBK_EARG;
+      if (hd && (klo % g->a_mask_align || khi % g->a_mask_align || g->a_mask_align < 1)) return WBK_EARG;
+      if (f16 && hd && g->a_mask_align % 8 != 0) return WBK_EARG;   // the split kernel stages whole octets (kernels.h)
+      if (!aligned16(g->A, start, 4)) return WBK_EARG;              // rows are read as float4
+      if (khi > klo && !inside(g->A, start + klo / 4 * 4, start + (khi + 3) / 4 * 4, 4)) return WBK_EARG;
+    }
+  }
+  // ---- B / W ----
+  if (!f16) {
+    if (g->ldb % 4 == 0 && (!inside(g->B, 0, Kc * g->ldb, 4) || !aligned16(g->B, 0, 4) || g->ldb < N)) return WBK_EARG;
+  } else {
+    if (g->W.off != 0 || g->W.bytes != K * N * 4 || g->Wh.off != 0 || g->Wl.off != 0) return WBK_EARG;
+    if (g->ldwt < K || g->Wh.bytes != g->Wl.bytes || g->Wh.bytes < ((N - 1) * g->ldwt + Kc) * 2 || !g->Wh.host || !g->Wl.host)
+      return WBK_EARG;
+    if (g->ldwt != K && g->ldwt % 8 == 0) return WBK_EARG;     // launch_split_weight_f16 writes dense [N][K] rows
+  }
+  // ---- C ----
+  const int64_t nsplit = g->ksplit > 1 ? g->ksplit : 1;
+  const int64_t ncb = g->c_block_cols > 0 ? (N + g->c_block_cols - 1) / g->c_block_cols : 1;
+  const int64_t cw = g->c_block_cols > 0 ? std::min<int64_t>(g->c_block_cols, N) : N;
+  if (g->c_split_stride < 0 || g->c_block_stride < 0 || g->ldc < cw) return WBK_EARG;
+  const int64_t c_hi = (nsplit - 1) * g->c_split_stride + (ncb - 1) * g->c_block_stride + (M - 1) * g->ldc + cw;
+  if (pieces_out) {
+    if (!f16) return WBK_EARG;                                   // only the split-precision kernel knows piece outputs
+    if (!g->Cl.host || g->Cl.bytes != g->Ch.bytes || g->Cl.off != g->Ch.off || !inside(g->Ch, 0, c_hi, 2)) return WBK_EARG;
+  } else if (!inside(g->C, 0, c_hi, 4)) {
+    return WBK_EARG;
+  }
+  // ---- epilogue operands ----
+  if (g->bias.host && !inside(g->bias, 0, N, 4)) return WBK_EARG;
+  if (g->residual_is_c && (pieces_out || g->residual.host)) return WBK_EARG;
+  if (g->residual.host && !inside(g->residual, 0, (M - 1) * g->ldr + N, 4)) return WBK_EARG;
+  if (g->aux.host) {
+    const int32_t* ix = (const int32_t*)g->aux_idx.host;
+    if (!ix || g->aux_idx.off != 0 || g->aux_idx.bytes < M * 4 || g->n_aux_rows < 1) return WBK_EARG;
+    for (int64_t m = 0; m < M; m++) if (ix[m] < 0 || ix[m] >= g->n_aux_rows) return WBK_EARG;
+    if (!inside(g->aux, 0, (g->n_aux_rows - 1) * g->ld_aux + N, 4)) return WBK_EARG;
+  }
+
+  Pool P;
+  char *dA = upload(P, g->A), *dAh = upload(P, g->Ah), *dAl = upload(P, g->Al), *dD = upload(P, g->desc), *dB = upload(P, g->B);
+  char *dW = upload(P, g->W), *dWh = upload(P, g->Wh), *dWl = upload(P, g->Wl), *dC = upload(P, g->C), *dCh = upload(P, g->Ch);
+  char *dCl = upload(P, g->Cl), *dbias = upload(P, g->bias), *dres = upload(P, g->residual), *daux = upload(P, g->aux);
+  char* dix = upload(P, g->aux_idx);
+  int* dflag = nullptr;
+  if (g->use_range_flag) {
+    void* p = nullptr;
+    if (P.ok(hipMalloc(&p, 4))) { P.dev.push_back(p); P.ok(hipMemset(p, 0, 4)); dflag = (int*)p; }
+  }
+  if (P.err) return P.err;
+  auto at = [](char* d, const WbkBuf& b) -> char* { return d ? d + b.off : nullptr; };
+
+  wb::GemmArgs a;
+  a.A = (const float*)at(dA, g->A); a.lda = g->lda;
+  a.a_desc = (const wb::RowDesc*)dD; a.a_mask_align = (int)g->a_mask_align; a.conv1_tstride = (int)g->conv1_tstride;
+  a.B = (const float*)at(dB, g->B); a.ldb = (int)g->ldb;
+  a.C = (float*)at(dC, g->C); a.ldc = (int)g->ldc;
+  a.bias = (const float*)at(dbias, g->bias);
+  a.residual = g->residual_is_c ? a.C : (const float*)at(dres, g->residual); a.ldr = (int)g->ldr;
+  a.aux = (const float*)at(daux, g->aux); a.aux_idx = (const int32_t*)dix; a.ld_aux = (int)g->ld_aux;
+  a.col_scale = (float)g->col_scale; a.col_scale_period = (int)g->col_scale_period; a.col_scale_width = (int)g->col_scale_width;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.act = (int)g->act;
+  a.ksplit = (int)g->ksplit; a.c_split_stride = g->c_split_stride;
+  a.c_block_cols = (int)g->c_block_cols; a.c_block_stride = g->c_block_stride;
+  a.range_flag = dflag;
+  a.Ah = (const uint16_t*)at(dAh, g->Ah); a.Al = (const uint16_t*)at(dAl, g->Al);
+  a.Ch = (uint16_t*)at(dCh, g->Ch); a.Cl = (uint16_t*)at(dCl, g->Cl);
+
+  int status;
+  if (f16) {
+    if (g->ldwt == K) wb::launch_split_weight_f16(nullptr, (const float*)dW, (int)K, (int)N, (uint16_t*)dWh, (uint16_t*)dWl);
+    status = wb::launch_gemm_f16x3(nullptr, a, (const uint16_t*)dWh, (const uint16_t*)dWl, (int)g->ldwt);
+  } else {
+    status = wb::launch_gemm_f32(nullptr, a);
+  }
+  status = finish(P, status);
+  if (status < -999) return status;
+  download(P, g->C, dC); download(P, g->Ch, dCh); download(P, g->Cl, dCl); download(P, g->Wh, dWh); download(P, g->Wl, dWl);
+  g->range_flag_out = 0;
+  if (dflag) { int v = 0; P.ok(hipMemcpy(&v, dflag, 4, hipMemcpyDeviceToHost)); g->range_flag_out = v; }
+  return P.err ? P.err : status;
+}
+
+struct WbkAttn {
+  int64_t which;                    // 0: launch_attention_f32, 1: launch_attention
+  WbkBuf X;                         // f32 array holding Q, K and V (fused-QKV or cross views): off unused
+  int64_t q_off, k_off, v_off;      // ELEMENT offsets of the three pointers in X
+  WbkBuf O, Oh, Ol, segs;           // O / Oh / Ol copied in and back; segs: AttnSeg[n_segs]
+  int64_t ldq, ldkv, ldo, n_segs, max_q_len, n_head, causal, split;
+  int64_t wrote_pieces;             // out: launch_attention's return value
+  double scale;
+};
+
+int wbk_attention(WbkAttn* t) {
+  const int64_t H = t->n_head, hd = 64;
+  if (t->n_segs < 1 || H < 1 || t->max_q_len < 1 || !t->X.host || t->X.off != 0 || !t->segs.host) return WBK_EARG;
+  if (t->segs.off != 0 || t->segs.bytes < t->n_segs * (int64_t)sizeof(wb::AttnSeg)) return WBK_EARG;
+  // the alignment contracts of kernels.h (rows are read and written as float4 / 8-byte piece groups)
+  if (t->ldq % 4 || t->ldkv % 4 || t->ldo % 4 || t->q_off % 4 || t->k_off % 4 || t->v_off % 4) return WBK_EARG;
+  if (t->ldq < H * hd || t->ldkv < H * hd || t->ldo < H * hd) return WBK_EARG;
+  const bool pieces = t->Oh.host && t->Ol.host;
+  if ((t->Oh.host != nullptr) != (t->Ol.host != nullptr)) return WBK_EARG;
+  if (pieces && (t->Oh.bytes != t->Ol.bytes || t->Oh.off != t->Ol.off || (t->Oh.off & 7))) return WBK_EARG;
+  if (!t->O.host || (t->O.off & 15)) return WBK_EARG;
+  const wb::AttnSeg* s = (const wb::AttnSeg*)t->segs.host;
+  const int64_t xe = t->X.bytes / 4;
+  for (int64_t i = 0; i < t->n_segs; i++) {
+    if (s[i].q_len < 0 || s[i].kv_len < 1 || s[i].q_len > t->max_q_len || s[i].q_row0 < 0 || s[i].kv_row0 < 0) return WBK_EARG;
+    if (s[i].q_len == 0) continue;
+    const int64_t qhi = t->q_off + (int64_t)(s[i].q_row0 + s[i].q_len - 1) * t->ldq + H * hd;
+    const int64_t khi = (int64_t)(s[i].kv_row0 + s[i].kv_len - 1) * t->ldkv + H * hd;
+    if (qhi > xe || t->k_off + khi > xe || t->v_off + khi > xe || t->q_off < 0 || t->k_off < 0 || t->v_off < 0) return WBK_EARG;
+    const int64_t olo = (int64_t)s[i].q_row0 * t->ldo, ohi = (int64_t)(s[i].q_row0 + s[i].q_len - 1) * t->ldo + H * hd;
+    if (!inside(t->O, olo, ohi, 4)) return WBK_EARG;
+    if (pieces && !inside(t->Oh, olo, ohi, 2)) return WBK_EARG;
+  }
+  Pool P;
+  char *dX = upload(P, t->X), *dO = upload(P, t->O), *dOh = upload(P, t->Oh), *dOl = upload(P, t->Ol), *dS = upload(P, t->segs);
+  if (P.err) return P.err;
+  const float* X = (const float*)dX;
+  float* O = (float*)(dO + t->O.off);
+  uint16_t* Oh = pieces ? (uint16_t*)(dOh + t->Oh.off) : nullptr;
+  uint16_t* Ol = pieces ? (uint16_t*)(dOl + t->Ol.off) : nullptr;
+  t->wrote_pieces = 0;
+  if (t->which == 0) {
+    wb::launch_attention_f32(nullptr, X + t->q_off, (int)t->ldq, X + t->k_off, X + t->v_off, (int)t->ldkv, O, (int)t->ldo,
+                             (const wb::AttnSeg*)dS, (int)t->n_segs, (int)t->max_q_len, (int)H, (float)t->scale, (int)t->causal);
+  } else {
+    t->wrote_pieces = wb::launch_attention(nullptr, X + t->q_off, (int)t->ldq, X + t->k_off, X + t->v_off, (int)t->ldkv, O,
+                                           (int)t->ldo, (const wb::AttnSeg*)dS, (int)t->n_segs, (int)t->max_q_len, (int)H,
+                                           (float)t->scale, (int)t->causal, t->split != 0, Oh, Ol) ? 1 : 0;
+  }
+  const int status = finish(P, 0);
+  if (status) return status;
+  download(P, t->O, dO); download(P, t->Oh, dOh); download(P, t->Ol, dOl);
+  return P.err;
+}
+
+struct WbkNorm {
+  int64_t which;                    // 0: launch_layernorm, 1: launch_layernorm_pieces, 2: launch_embed
+  WbkBuf x, g, b;                   // LayerNorm: x [M][d], g [d], b [d].  embed: x = E [n_vocab][d], g = pos [L][d], b = tok (int32 [M])
+  WbkBuf y, yh, yl;                 // outputs (copied in and back): y f32, or the pieces
+  int64_t M, d, eps_inside_sqrt, L, n_vocab;
+  double eps;
+};
+
+int wbk_norm(WbkNorm* t) {
+  const int64_t M = t->M, d = t->d;
+  if (M < 1 || d < 1 || M > (1 << 20) || d > (1 << 20)) return WBK_EARG;
+  if (d % 4 != 0) return WBK_EARG;                              // kernels.h: rows are read as float4
+  Pool P;
+  if (t->which == 2) {
+    const int32_t* tok = (const int32_t*)t->b.host;
+    if (!tok || t->b.off != 0 || t->b.bytes < M * 4 || t->L < 1 || t->n_vocab < 1) return WBK_EARG;
+    for (int64_t r = 0; r < M; r++) if (tok[r] < 0 || tok[r] >= t->n_vocab) return WBK_EARG;
+    if (!inside(t->x, 0, t->n_vocab * d, 4) || !inside(t->g, 0, std::min(M, t->L) * d, 4) || !inside(t->y, 0, M * d, 4)) return WBK_EARG;
+    if (!aligned16(t->x, 0, 4) || !aligned16(t->g, 0, 4) || !aligned16(t->y, 0, 4)) return WBK_EARG;
+    char *dE = upload(P, t->x), *dpos = upload(P, t->g), *dtok = upload(P, t->b), *dy = upload(P, t->y);
+    if (P.err) return P.err;
+    wb::launch_embed(nullptr, (const int32_t*)dtok, (int)M, (int)t->L, (int)d, (const float*)(dE + t->x.off),
+                     (const float*)(dpos + t->g.off), (float*)(dy + t->y.off));
+    const int status = finish(P, 0);
+    if (status) return status;
+    download(P, t->y, dy);
+    return P.err;
+  }
+  if (!inside(t->x, 0, M * d, 4) || !inside(t->g, 0, d, 4) || !inside(t->b, 0, d, 4)) return WBK_EARG;
+  if (!aligned16(t->x, 0, 4) || !aligned16(t->g, 0, 4) || !aligned16(t->b, 0, 4)) return WBK_EARG;
+  if (t->which == 0) {
+    if (!inside(t->y, 0, M * d, 4) || !aligned16(t->y, 0, 4)) return WBK_EARG;
+  } else {
+    if (!t->yl.host || t->yl.bytes != t->yh.bytes || t->yl.off != t->yh.off || !inside(t->yh, 0, M * d, 2) || (t->yh.off & 7))
+      return WBK_EARG;
+  }
+  char *dx = upload(P, t->x), *dg = upload(P, t->g), *db = upload(P, t->b);
+  char *dy = upload(P, t->y), *dyh = upload(P, t->yh), *dyl = upload(P, t->yl);
+  if (P.err) return P.err;
+  if (t->which == 0)
+    wb::launch_layernorm(nullptr, (const float*)(dx + t->x.off), (float*)(dy + t->y.off), (int)M, (int)d,
+                         (const float*)(dg + t->g.off), (const float*)(db + t->b.off), (float)t->eps, (int)t->eps_inside_sqrt);
+  else
+    wb::launch_layernorm_pieces(nullptr, (const float*)(dx + t->x.off), (uint16_t*)(dyh + t->yh.off), (uint16_t*)(dyl + t->yl.off),
+                                (int)M, (int)d, (const float*)(dg + t->g.off), (const float*)(db + t->b.off), (float)t->eps,
+                                (int)t->eps_inside_sqrt);
+  const int status = finish(P, 0);
+  if (status) return status;
+  download(P, t->y, dy); download(P, t->yh, dyh); download(P, t->yl, dyl);
+  return P.err;
+}
+
+struct WbkSkinny {
+  WbkBuf A, B;                      // A [M][lda] f32, B [K][N] f32 dense (ldb == N)
+  WbkBuf th, tl;                    // pieces variant (both non-null): made on the device from B by launch_split_weight_f16_tiles
+                                    // ([N / 16][K / 32][4][16][8] fp16, exactly K * N halves each), copied back
+  WbkBuf P;                         // split-K planes, copied in and back
+  int64_t lda, M, N, K, ksplit, plane, use_range_flag, range_flag_out;
+};
+
+int wbk_skinny_ksplit(int K, int N, int max_ks, int max_rows) { return wb::skinny_ksplit(K, N, max_ks, max_rows); }
+int wbk_skinny_supported(int M, int K, int N) { return wb::skinny_supported(M, K, N) ? 1 : 0; }
+
+int wbk_skinny(WbkSkinny* t) {
+  const int64_t M = t->M, N = t->N, K = t->K;
+  if (M < 1 || M > 64 || N < 1 || K < 1 || N > (1 << 20) || K > (1 << 20) || t->ksplit < 1) return WBK_EARG;
+  const bool pieces = t->th.host != nullptr;
+  if (t->lda % 4 || t->lda < K || !inside(t->A, 0, (M - 1) * t->lda + K, 4) || !aligned16(t->A, 0, 4)) return WBK_EARG;
+  if (t->B.off != 0 || t->B.bytes != K * N * 4 || !t->B.host) return WBK_EARG;
+  if (t->plane < M * N || !inside(t->P, 0, (t->ksplit - 1) * t->plane + M * N, 4) || !aligned16(t->P, 0, 4) || t->plane % 4) return WBK_EARG;
+  if (pieces && (K % 32 || N % 16 || !t->tl.host || t->th.off || t->tl.off || t->th.bytes != K * N * 2 || t->tl.bytes != K * N * 2))
+    return WBK_EARG;
+  Pool Pl;
+  char *dA = upload(Pl, t->A), *dB = upload(Pl, t->B), *dth = upload(Pl, t->th), *dtl = upload(Pl, t->tl), *dP = upload(Pl, t->P);
+  int* dflag = nullptr;
+  if (t->use_range_flag) {
+    void* p = nullptr;
+    if (Pl.ok(hipMalloc(&p, 4))) { Pl.dev.push_back(p); Pl.ok(hipMemset(p, 0, 4)); dflag = (int*)p; }
+  }
+  if (Pl.err) return Pl.err;
+  wb::SkinnyArgs a;
+  a.A = (const float*)(dA + t->A.off); a.lda = (int)t->lda;
+  a.B = (const float*)dB; a.ldb = (int)N;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K; a.ksplit = (int)t->ksplit;
+  a.P = (float*)(dP + t->P.off); a.plane = (int)t->plane;
+  a.range_flag = dflag;
+  if (pieces) {
+    wb::launch_split_weight_f16_tiles(nullptr, (const float*)dB, (int)K, (int)N, (uint16_t*)dth, (uint16_t*)dtl);
+    a.Bh = (const uint16_t*)dth; a.Bl = (const uint16_t*)dtl;
+  }
+  int status = wb::launch_dec_skinny_gemm(nullptr, a);
+  status = finish(Pl, status);
+  if (status < -999) return status;
+  download(Pl, t->P, dP); download(Pl, t->th, dth); download(Pl, t->tl, dtl);
+  t->range_flag_out = 0;
+  if (dflag) { int v = 0; Pl.ok(hipMemcpy(&v, dflag, 4, hipMemcpyDeviceToHost)); t->range_flag_out = v; }
+  return Pl.err ? Pl.err : status;
+}
+
+const char* wbk_version() { return "whisper_hip kernel test harness 1"; }
+
+}  // extern "C"
