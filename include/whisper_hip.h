@@ -376,6 +376,47 @@ int wb_stitch_windows(const int32_t* win_tokens, int32_t row_stride, const int32
                       int n_windows, int max_n_offsets, int min_n_overlaps, int32_t* out,
                       int64_t cap, int64_t* n_out);
 
+/* ---- token timestamps: cross-attention alignment + DTW (the technique behind `word_timestamps`) ------------------
+ * The reference decodes with <|notimestamps|> (transcribe.rs:203); token times come from the decoder's cross-attention
+ * instead.  Per row: one teacher-forced pass of the decoder over the finished tokens; for every alignment head the
+ * softmax weights W[l][c] over the window's C encoder positions (exact f32); z-score over the token axis per position
+ * (biased variance; a constant column gives zeros); median filter of width filter_width along c (reflect padding; skipped
+ * when C <= filter_width / 2); M = mean over the heads; DTW over X = -M[n_prefix .. len - drop_last) in f32 (strict
+ * comparisons, diagonal before up before left).  A token's start position is the column of the first path cell of its
+ * row; its time is window start + 0.02 s * position.  All of it runs on the device (align.hip).
+ *
+ * heads: n_heads pairs (layer, head); NULL / 0 = every head of layers [n_text_layer / 2, n_text_layer).  The pass meets
+ *        the layers in ascending order; heads of one layer are summed in the order given.
+ * lens:  per-row length, NULL = L.  start_pos [n][L]: entry l of a DTW row = its start position, every other entry -1.
+ * matrix (optional, parity / debug): M, [n][L][C], zero outside a row's len.
+ * Errors (nothing is launched): unknown layer / head, filter_width even or outside 1 .. 15, n_prefix + drop_last >= len
+ * -> WB_ERR_ARG; len > n_text_ctx -> WB_ERR_SHAPE. */
+int wb_align_tokens(wb_model* m, const int32_t* tokens, int n, int L, const int32_t* lens, const float* enc, int C,
+                    const int32_t* heads, int32_t n_heads, int32_t n_prefix, int32_t drop_last, int32_t filter_width,
+                    int32_t* start_pos, float* matrix);
+/* The same over a session's windows, after (or without) a decode: row w belongs to window w and uses the session's
+ * encoder output and cached cross-attention K -- no re-encode.  start_pos [W][row_stride]; matrix [W][row_stride][maxC]
+ * (maxC: the largest C of the session's windows). */
+int wb_session_align(wb_session* s, const int32_t* tokens, int32_t row_stride, const int32_t* lens, const int32_t* heads,
+                     int32_t n_heads, int32_t n_prefix, int32_t drop_last, int32_t filter_width, int32_t* start_pos,
+                     float* matrix);
+/* The DTW alone on a caller's f32 cost matrix x [N][C] (host memory): start position of every row.  N <= 512.
+ * `device` only hosts the buffers (no model). */
+int wb_dtw_start_positions(int device, const float* x, int32_t N, int32_t C, int32_t* start_pos);
+/* wb_waveform_to_tokens + alignment of every window's row as decoded (n_prefix = 4, the prompt; drop_last = 1 exactly when
+ * the row ends in tok_end_of_text), on the session that decoded it.  win_times [n_local][row_stride]: seconds from the
+ * start of the waveform, NaN where the token is not aligned; stitched_times parallel to `stitched` (required with it). */
+int wb_waveform_to_token_times(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                               const uint8_t* is_special, int win_begin, int win_end, int32_t* win_tokens,
+                               int32_t row_stride, int32_t* win_lens, int32_t* stitched, int64_t stitched_cap,
+                               int64_t* n_stitched, const int32_t* heads, int32_t n_heads, int32_t filter_width,
+                               float* win_times, float* stitched_times);
+/* wb_stitch_windows carrying a parallel float per token (win_times [n_windows][row_stride]) through the same fold: a
+ * stitched token keeps the value it had in the window the stitch took it from (transcribe.rs:56-63).  Host only. */
+int wb_stitch_windows_times(const int32_t* win_tokens, int32_t row_stride, const int32_t* win_lens, int n_windows,
+                            int max_n_offsets, int min_n_overlaps, int32_t* out, int64_t cap, int64_t* n_out,
+                            const float* win_times, float* out_times);
+
 /* The reference's retired greedy decoder kept its repetition detectors (transcribe.rs:385-447, dead code there):
  *   wb_first_repetition_end        :385-393   (period > n, a usize underflow panic there -> WB_ERR_ARG)
  *   wb_repetition_period           :395-417   returns the period, 0 for None

@@ -91,6 +91,22 @@ extern "C" {
                                  p: *const wb_decode_params, is_special: *const u8, win_begin: c_int, win_end: c_int,
                                  win_tokens: *mut i32, row_stride: i32, win_lens: *mut i32, stitched: *mut i32,
                                  stitched_cap: i64, n_stitched: *mut i64) -> c_int;
+    // token timestamps: cross-attention alignment + DTW on the device (no counterpart in the reference)
+    pub fn wb_align_tokens(m: *mut wb_model, tokens: *const i32, n: c_int, L: c_int, lens: *const i32, enc: *const c_float,
+                           C: c_int, heads: *const i32, n_heads: i32, n_prefix: i32, drop_last: i32, filter_width: i32,
+                           start_pos: *mut i32, matrix: *mut c_float) -> c_int;
+    pub fn wb_session_align(s: *mut wb_session, tokens: *const i32, row_stride: i32, lens: *const i32, heads: *const i32,
+                            n_heads: i32, n_prefix: i32, drop_last: i32, filter_width: i32, start_pos: *mut i32,
+                            matrix: *mut c_float) -> c_int;
+    pub fn wb_dtw_start_positions(device: c_int, x: *const c_float, N: i32, C: i32, start_pos: *mut i32) -> c_int;
+    pub fn wb_waveform_to_token_times(m: *mut wb_model, pcm: *const c_float, n: i64, sample_rate: c_int,
+                                      p: *const wb_decode_params, is_special: *const u8, win_begin: c_int, win_end: c_int,
+                                      win_tokens: *mut i32, row_stride: i32, win_lens: *mut i32, stitched: *mut i32,
+                                      stitched_cap: i64, n_stitched: *mut i64, heads: *const i32, n_heads: i32,
+                                      filter_width: i32, win_times: *mut c_float, stitched_times: *mut c_float) -> c_int;
+    pub fn wb_stitch_windows_times(win_tokens: *const i32, row_stride: i32, win_lens: *const i32, n_windows: c_int,
+                                   max_n_offsets: c_int, min_n_overlaps: c_int, out: *mut i32, cap: i64, n_out: *mut i64,
+                                   win_times: *const c_float, out_times: *mut c_float) -> c_int;
     pub fn wb_session_begin(m: *mut wb_model, pcm: *const c_float, n_pcm: i64, starts: *const i64, lens: *const i64,
                             n_windows: c_int, max_beams: c_int, padding: c_int, out: *mut *mut wb_session) -> c_int;
     pub fn wb_session_set_special_mask(s: *mut wb_session, is_special: *const u8) -> c_int;

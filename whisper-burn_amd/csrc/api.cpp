@@ -53,7 +53,7 @@ void DevMem::release() {
 }
 
 // One lock per process for the stateless entry points (they share the model's scratch workspace).
-static std::mutex g_stateless_mu;
+std::mutex g_stateless_mu;
 
 }  // namespace wb
 

@@ -467,4 +467,113 @@ static int run_decoder_stateless_body(wb_model* m, hipStream_t st, Workspace& ws
   return WB_OK;
 }
 
+int run_align(wb_model* m, hipStream_t st, Workspace& ws, AlignJob& J) {
+  const wb_dims& D = m->dims;
+  const int d = D.n_text_state, H = D.n_text_head, NL = D.n_text_layer;
+  const int n = J.n, L = J.L, rows = n * L, S = (int)J.head_id.size();
+  WB_REQUIRE(n > 0 && L > 0 && L <= ALIGN_MAX_LEN && S > 0 && d == 64 * H, WB_ERR_SHAPE, "align: unsupported shape");
+  const int last_layer = J.head_layer.back();
+  AlignBufs& B = ws.align;
+  J.segs_host.resize(2 * n); J.dtw_host.resize(n);
+  int maxC = 0, maxN = 0;
+  for (int i = 0; i < n; i++) {
+    J.segs_host[i] = AttnSeg{i * L, J.len[i], i * L, J.len[i]};              // masked self-attention
+    J.segs_host[n + i] = AttnSeg{i * L, J.len[i], J.kv_row0[i], J.C[i]};     // cross-attention
+    const int N = std::max(0, J.len[i] - J.n_prefix - (J.drop_rows.empty() ? J.drop_last : J.drop_rows[i]));
+    J.dtw_host[i] = DtwSeg{i * L + J.n_prefix, N, J.C[i], i * L + J.n_prefix};
+    maxC = std::max(maxC, J.C[i]); maxN = std::max(maxN, N);
+  }
+  J.maxC = maxC;
+  const int ldt = (maxC + 3) / 4;
+  WB_TRY(upload(st, ws.segs, J.segs_host.data(), J.segs_host.size() * sizeof(AttnSeg)));
+  ws.enc_T.clear();                   // (ws.segs no longer holds the encoder's segments)
+  WB_TRY(upload(st, B.tok_dev, J.tokens.data(), J.tokens.size() * 4));
+  WB_TRY(upload(st, B.heads_dev, J.head_id.data(), J.head_id.size() * 4));
+  WB_TRY(upload(st, B.dtw_segs, J.dtw_host.data(), J.dtw_host.size() * sizeof(DtwSeg)));
+  int max_nh = 0;                                // most alignment heads on one layer: what one statistics launch writes
+  for (int a = 0, b = 0; a < S; a = b) {
+    while (b < S && J.head_layer[b] == J.head_layer[a]) b++;
+    max_nh = std::max(max_nh, b - a);
+  }
+  WB_TRY(B.stats.ensure((size_t)max_nh * rows * sizeof(float2)));
+  WB_TRY(B.trace.ensure((size_t)n * std::max(maxN, 1) * ldt * 4));
+  WB_TRY(B.M.ensure((size_t)rows * maxC * 4));
+  WB_TRY(B.start.ensure((size_t)rows * 4));
+  WB_HIP(hipMemsetAsync(B.start.p, 0xFF, (size_t)rows * 4, st));   // -1: not a DTW row
+  WB_HIP(hipMemsetAsync(B.M.p, 0, (size_t)rows * maxC * 4, st));   // (entries past a row's len / C are never written)
+  WB_TRY(ws.x.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.h.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.qkv.ensure((size_t)rows * 3 * d * 4));
+  WB_TRY(ws.att.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.hm.ensure((size_t)rows * 4 * d * 4));
+  float *x = ws.x.as<float>(), *h = ws.h.as<float>(), *qkv = ws.qkv.as<float>(), *att = ws.att.as<float>(),
+        *hm = ws.hm.as<float>();
+  const AttnSeg* sg = ws.segs.as<AttnSeg>();
+  const float* ckv = J.ckv;
+  int64_t layer_stride = J.ckv_layer_stride;
+  int ldkv = J.ldkv;
+  GemmArgs g;
+  if (J.enc_dev) {   // cross K|V of every layer in one GEMM, K pre-scaled (as run_decoder_stateless_body)
+    ldkv = NL * 2 * d; layer_stride = 2 * d;
+    WB_TRY(ws.x1.ensure((size_t)J.enc_rows * ldkv * 4));
+    g = linear_args(J.enc_dev, J.enc_rows, m->ckv_all, ws.x1.as<float>());
+    g.col_scale = m->qk_scale; g.col_scale_period = 2 * d; g.col_scale_width = d;
+    WB_TRY(gemm(m, st, g, &m->ckv_all));
+    ckv = ws.x1.as<float>();
+  }
+  // Rows are packed with stride L: positions past a row's len carry token 0 and go through every GEMM / LayerNorm of the
+  // pass, and their attention outputs are never written (q_len masks them), so workspace contents flow through them.
+  // That is sound only because every operator here is row-independent and the decoder weights carry no split copy: the
+  // GEMMs run on the exact-f32 kernel, whose range guard does not exist, and nothing reads those rows' results.
+  launch_embed(st, B.tok_dev.as<int32_t>(), rows, L, d, m->tok_emb, m->dec_pos, x);
+  int h0 = 0;                                    // first alignment head of the current layer
+  for (int i = 0; i <= last_layer; i++) {        // ResidualDecoderAttentionBlock::forward, mod.rs:345-350
+    const DecBlockW& b = m->dec[i];
+    launch_layernorm(st, x, h, rows, d, b.ln1.g, b.ln1.b, b.ln1.eps, m->ln_eps_inside_sqrt);
+    g = linear_args(h, rows, b.qkv, qkv);
+    g.col_scale = m->qk_scale; g.col_scale_period = 3 * d; g.col_scale_width = 2 * d;
+    WB_TRY(gemm(m, st, g, &b.qkv));
+    launch_attention_f32(st, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, sg, n, L, H, 1.0f, 1);
+    g = linear_args(att, rows, b.out, x);
+    g.residual = x; g.ldr = d;
+    WB_TRY(gemm(m, st, g, &b.out));
+    launch_layernorm(st, x, h, rows, d, b.ln2.g, b.ln2.b, b.ln2.eps, m->ln_eps_inside_sqrt);
+    g = linear_args(h, rows, b.cq, qkv);
+    g.col_scale = m->qk_scale; g.col_scale_period = d; g.col_scale_width = d;
+    WB_TRY(gemm(m, st, g, &b.cq));
+    const float* Kl = ckv + (size_t)i * layer_stride;
+    int h1 = h0;
+    while (h1 < S && J.head_layer[h1] == i) h1++;
+    if (h1 > h0) {
+      const int nh = h1 - h0;
+      const int32_t* hd = B.heads_dev.as<int32_t>() + h0;
+      prof_tag(KC_ALIGN_STATS, 0);
+      launch_align_row_stats(st, qkv, d, Kl, ldkv, sg + n, n, L, hd, nh, B.stats.as<float2>(), L);
+      prof_tag(KC_ALIGN_ACCUM, 0);
+      WB_REQUIRE(launch_align_accumulate(st, qkv, d, Kl, ldkv, sg + n, n, L, maxC, hd, nh, B.stats.as<float2>(), L,
+                                         B.M.as<float>(), L, maxC, J.filter_width, h0 == 0, h1 == S ? S : 0) == 0,
+                 WB_ERR_SHAPE, "align: unsupported shape (len %d, filter width %d)", L, J.filter_width);
+      h0 = h1;
+    }
+    if (i == last_layer) break;                  // nothing after the last alignment layer's query is needed
+    launch_attention_f32(st, qkv, d, Kl, Kl + d, ldkv, att, d, sg + n, n, L, H, 1.0f, 0);
+    g = linear_args(att, rows, b.cout, x);
+    g.residual = x; g.ldr = d;
+    WB_TRY(gemm(m, st, g, &b.cout));
+    launch_layernorm(st, x, h, rows, d, b.ln3.g, b.ln3.b, b.ln3.eps, m->ln_eps_inside_sqrt);
+    g = linear_args(h, rows, b.mlp1, hm);
+    g.act = ACT_GELU;
+    WB_TRY(gemm(m, st, g, &b.mlp1));
+    WB_TRY(gemm_residual_kblocked(m, st, hm, rows, b.mlp2, x));
+  }
+  if (maxN > 0) {                                // (no row with a DTW row: every position stays -1)
+    prof_tag(KC_ALIGN_DTW, 0);
+    WB_REQUIRE(launch_align_dtw(st, B.M.as<float>(), maxC, 1, B.dtw_segs.as<DtwSeg>(), n, maxN, B.trace.as<uint32_t>(),
+                                (int64_t)maxN * ldt, ldt, B.start.as<int32_t>()) == 0,
+               WB_ERR_SHAPE, "align: DTW of %d rows unsupported", maxN);
+  }
+  WB_HIP(hipGetLastError());
+  return WB_OK;
+}
+
 }  // namespace wb

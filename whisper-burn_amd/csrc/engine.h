@@ -39,6 +39,27 @@ bool split_guard_resolve(wb_model* m, int* flag_host);
 int run_decoder_stateless(wb_model* m, hipStream_t st, Workspace& ws, const int32_t* tokens_dev, int n, int L,
                           const float* enc_dev, int C, float* logits_dev);
 
+// Token alignment (align.hip): one teacher-forced pass of the decoder over n token rows, stopped after the query projection
+// of the last layer that owns an alignment head; two launches per such layer fold its heads' cross-attention weights into
+// M, one DTW launch turns M into start positions.  Everything is enqueued on `st`; the caller synchronises once.
+struct AlignJob {
+  int n = 0, L = 0;                       // rows; row stride of tokens / M / start_pos (>= every len)
+  std::vector<int32_t> tokens;            // [n][L], entries past a row's len: any valid id
+  std::vector<int> len, C, kv_row0;       // per row: tokens, encoder positions, first row of its window in the K source
+  const float* enc_dev = nullptr;         // non-null: project the cross K here (enc_rows x d input); else use ckv
+  int enc_rows = 0;
+  const float* ckv = nullptr;             // cached pre-scaled cross K|V: layer i at ckv + i * ckv_layer_stride, rows of ldkv
+  int64_t ckv_layer_stride = 0; int ldkv = 0;
+  std::vector<int32_t> head_layer, head_id;   // the alignment heads, layers ascending
+  int n_prefix = 0, drop_last = 0, filter_width = 7, maxC = 0;
+  std::vector<int> drop_rows;             // per-row drop_last (empty: drop_last for every row)
+  // host arrays staged to the device by run_align: they live here so that they outlive the enqueued copies
+  // (the device side is the workspace's AlignBufs)
+  std::vector<AttnSeg> segs_host; std::vector<DtwSeg> dtw_host;
+};
+int run_align(wb_model* m, hipStream_t st, Workspace& ws, AlignJob& job);
+extern std::mutex g_stateless_mu;       // api.cpp: serialises the stateless entry points (they share the model's scratch)
+
 // split-precision fp16 MFMA GEMM when split copies sh / sl ([N][ldwt] fp16) are given and the shape fits, else exact-f32 MFMA
 int gemm_dispatch(const wb_model* m, hipStream_t st, const GemmArgs& a, int ldwt, const uint16_t* sh = nullptr,
                   const uint16_t* sl = nullptr);

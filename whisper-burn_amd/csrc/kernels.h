@@ -16,6 +16,8 @@ enum KernelClass {
   // batch mode (more than 8 live rows): one class per kernel of the per-layer chain
   KC_B_RESOLVE_LN, KC_B_GEMM, KC_B_SELF_ATTN, KC_B_CROSS_STREAM, KC_B_CROSS_CHUNK, KC_B_COMBINE, KC_B_GELU_FOLD,
   KC_B_LOGITS_GEMM, KC_B_TOPK_ROWS, KC_PERSIST, KC_BEAM_UPDATE, KC_FOLD_LN_ROWS,
+  // token alignment (align.hip): at most two launches per decoder layer that owns an alignment head, one DTW launch
+  KC_ALIGN_STATS, KC_ALIGN_ACCUM, KC_ALIGN_DTW,
   KC_COUNT
 };
 void prof_tag(int cls, double algo_bytes);
@@ -150,5 +152,25 @@ void launch_attention_f32(hipStream_t st, const float* Q, int ldq, const float* 
 bool launch_attention(hipStream_t st, const float* Q, int ldq, const float* K, const float* V, int ldkv,
                       float* O, int ldo, const AttnSeg* segs_dev, int n_segs, int max_q_len, int n_head,
                       float scale, int causal, bool split, uint16_t* Oh = nullptr, uint16_t* Ol = nullptr);
+
+// ---- token alignment (align.hip): kept cross-attention weights -> z-score / median / head mean -> DTW ----------------
+// Q [rows][ldq] and K [kv rows][ldkv] are the PRE-SCALED cross-attention query / key of one decoder layer (head size 64,
+// float4 reads: ldq % 4 == 0, ldkv % 4 == 0, 16-byte aligned); segs as for attention (q_row0 / q_len: the token row,
+// kv_row0 / kv_len: its window's encoder positions, kv_len >= 1); heads_dev: the layer's alignment heads in order.
+constexpr int ALIGN_MAX_LEN = 448;
+// stats[(h * n_rows + row) * ld_stats + q] = (max, sum exp(s - max)) of score row (heads_dev[h], row, q)
+void launch_align_row_stats(hipStream_t st, const float* Q, int ldq, const float* K, int ldkv, const AttnSeg* segs_dev,
+                            int n_rows, int max_len, const int32_t* heads_dev, int n_heads, float2* stats, int ld_stats);
+// M[(row * ld_row + q) * ldm + c] (+)= median_c(zscore_q(softmax weights)) of every head of the list, in order.
+// first != 0: the list starts the whole head set (M is written); n_total > 0: it ends it (M = sum / n_total).
+// filter_width odd, 1 .. 15; max_len <= ALIGN_MAX_LEN.  Returns 0, or -1 for an unsupported shape (nothing launched).
+int launch_align_accumulate(hipStream_t st, const float* Q, int ldq, const float* K, int ldkv, const AttnSeg* segs_dev,
+                            int n_rows, int max_len, int max_C, const int32_t* heads_dev, int n_heads, const float2* stats,
+                            int ld_stats, float* M, int ld_row, int ldm, int filter_width, int first, int n_total);
+// DTW over x[i][j] = (negate ? -1 : 1) * X[(x_row0 + i) * ldx + j], i < n, j < c: out[out0 + i] = column of the first path
+// cell of row i.  trace: n_rows * trace_stride words, trace_stride >= max_n * ldt, ldt >= ceil(max c / 4).  n <= 512.
+struct DtwSeg { int32_t x_row0, n, c, out0; };
+int launch_align_dtw(hipStream_t st, const float* X, int ldx, int negate, const DtwSeg* segs_dev, int n_rows, int max_n,
+                     uint32_t* trace, int64_t trace_stride, int ldt, int32_t* out);
 
 }  // namespace wb

@@ -98,4 +98,9 @@ int session_beam_chain(wb_session* s, const int32_t* prompt, int prompt_len, int
                        int mask_until_len, int32_t* out_tokens, int32_t row_stride, int32_t* out_lens, bool* handled);
 int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_depth, int mask_until_len, int prompt_len,
                          int32_t* out_tokens, int32_t row_stride, int32_t* out_lens);
+// wb_session_align (align.cpp); drop_last_rows non-null: drop_last per window instead of the scalar, and a row that leaves
+// no DTW row is accepted (all its positions stay -1)
+int session_align(wb_session* s, const int32_t* tokens, int32_t row_stride, const int32_t* lens, const int32_t* heads,
+                  int32_t n_heads, int32_t n_prefix, int32_t drop_last, int32_t filter_width, int32_t* start_pos,
+                  float* matrix, const int32_t* drop_last_rows);
 }  // namespace wb

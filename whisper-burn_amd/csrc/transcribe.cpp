@@ -2,6 +2,7 @@
 // session API: window extents, beam search, token-overlap stitch.  Pure integer / f64 host
 // logic, restated exactly (property-tested against the Python restatement in oracle/).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -401,10 +402,13 @@ extern "C" int wb_beam_search(const wb_decode_params* p, int n_windows, int n_vo
                              row_stride, out_lens);
 }
 
+// token times (wb_waveform_to_token_times): each window's row is aligned on the session that decoded it
+struct TokenTimes { const int32_t* heads; int32_t n_heads, filter_width; float* win_times; float* stitched_times; };
+
 static int waveform_to_tokens_impl(wb_model* m, const float* pcm, bool pcm_on_device, int64_t n, int sample_rate,
                                    const wb_decode_params* p, const uint8_t* is_special, int win_begin, int win_end,
                                    int32_t* win_tokens, int32_t row_stride, int32_t* win_lens, int32_t* stitched,
-                                   int64_t stitched_cap, int64_t* n_stitched) {
+                                   int64_t stitched_cap, int64_t* n_stitched, const TokenTimes* tt = nullptr) {
   WB_REQUIRE(m && pcm && p && is_special && win_tokens && win_lens, WB_ERR_ARG, "wb_waveform_to_tokens: null argument");
   wb::GpuTurn turn(m->device);   // (the sharded entry point calls this for its local windows and exchanges results outside the turn)
   WB_REQUIRE(p->padding >= 0 && p->padding < m->max_mel_frames(), WB_ERR_ARG, "bad padding");
@@ -440,12 +444,32 @@ static int waveform_to_tokens_impl(wb_model* m, const float* pcm, bool pcm_on_de
         rc = WB_OK;                            // (whatever the decode made of the non-finite encoder output is void)
         session_rewind(s);                     // back to step 0 over the re-encoded window batch
       }
+      if (rc == WB_OK && tt) {
+        // prompt tokens are not aligned; a final <|endoftext|> takes part in the pass but is no DTW row
+        const int32_t* rows = win_tokens + (size_t)b0 * row_stride;
+        std::vector<int32_t> drop(nb), pos((size_t)nb * row_stride);
+        for (int w = 0; w < nb; w++)
+          drop[w] = win_lens[b0 + w] > 0 && rows[(size_t)w * row_stride + win_lens[b0 + w] - 1] == p->tok_end_of_text;
+        rc = session_align(s, rows, row_stride, win_lens + b0, tt->heads, tt->n_heads, 4, 0, tt->filter_width, pos.data(),
+                           nullptr, drop.data());
+        for (int w = 0; rc == WB_OK && w < nb; w++) {
+          const double t0 = (double)starts[win_begin + b0 + w] / (double)sample_rate;
+          for (int l = 0; l < row_stride; l++) {
+            const int32_t q = pos[(size_t)w * row_stride + l];
+            tt->win_times[(size_t)(b0 + w) * row_stride + l] = q < 0 ? std::nanf("") : (float)(t0 + 0.02 * q);
+          }
+        }
+      }
       wb_session_free(s);
     }
     return rc;
   };
   for (int bi = 0; bi < n_batches; bi++) WB_TRY(run_batch(bi));
-  if (stitched) {
+  if (stitched && tt) {
+    WB_REQUIRE(n_stitched && tt->stitched_times, WB_ERR_ARG, "n_stitched / stitched_times is null");
+    WB_TRY(wb_stitch_windows_times(win_tokens, row_stride, win_lens, n_local, p->max_n_offsets, p->min_n_overlaps, stitched,
+                                   stitched_cap, n_stitched, tt->win_times, tt->stitched_times));
+  } else if (stitched) {
     WB_REQUIRE(n_stitched, WB_ERR_ARG, "n_stitched is null");
     WB_TRY(wb_stitch_windows(win_tokens, row_stride, win_lens, n_local, p->max_n_offsets, p->min_n_overlaps, stitched,
                              stitched_cap, n_stitched));
@@ -467,4 +491,17 @@ extern "C" int wb_waveform_to_tokens_dev(wb_model* m, const float* pcm_dev, int6
                                          int32_t* stitched, int64_t stitched_cap, int64_t* n_stitched) {
   return waveform_to_tokens_impl(m, pcm_dev, true, n, sample_rate, p, is_special, win_begin, win_end, win_tokens,
                                  row_stride, win_lens, stitched, stitched_cap, n_stitched);
+}
+
+extern "C" int wb_waveform_to_token_times(wb_model* m, const float* pcm, int64_t n, int sample_rate,
+                                          const wb_decode_params* p, const uint8_t* is_special, int win_begin, int win_end,
+                                          int32_t* win_tokens, int32_t row_stride, int32_t* win_lens, int32_t* stitched,
+                                          int64_t stitched_cap, int64_t* n_stitched, const int32_t* heads, int32_t n_heads,
+                                          int32_t filter_width, float* win_times, float* stitched_times) {
+  WB_REQUIRE(win_times && (stitched_times || !stitched), WB_ERR_ARG, "wb_waveform_to_token_times: null times buffer");
+  WB_REQUIRE(filter_width >= 1 && filter_width <= 15 && (filter_width & 1), WB_ERR_ARG,
+             "wb_waveform_to_token_times: filter_width %d must be odd and in 1 .. 15", filter_width);
+  const TokenTimes tt{heads, n_heads, filter_width, win_times, stitched_times};
+  return waveform_to_tokens_impl(m, pcm, false, n, sample_rate, p, is_special, win_begin, win_end, win_tokens, row_stride,
+                                 win_lens, stitched, stitched_cap, n_stitched, &tt);
 }

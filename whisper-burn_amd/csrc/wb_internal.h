@@ -121,8 +121,12 @@ struct DecBlockW {
   LinearW mlp1, mlp2;
 };
 
+// Device buffers of the token alignment (engine.cpp: run_align), grow-only like the rest of the workspace
+struct AlignBufs { DevMem tok_dev, heads_dev, stats, dtw_segs, trace, M, start; };
+
 // Grow-only device workspace shared by the forward passes of one owner (model scratch or session).
 struct Workspace {
+  AlignBufs align;
   DevMem x1, x, h, qkv, att, hm, desc1, desc2, auxidx, segs, misc;
   // geometry the encoder descriptors on the device were built for: a transcription loop over equally shaped batches
   // (the common case) re-uses them instead of paying four uploads and a stream synchronisation per batch

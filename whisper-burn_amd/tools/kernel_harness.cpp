@@ -338,6 +338,80 @@ int wbk_skinny(WbkSkinny* t) {
   return Pl.err ? Pl.err : status;
 }
 
+// token alignment (align.hip).  stages bit 0: launch_align_row_stats, bit 1: launch_align_accumulate (reads `stats`: run both,
+// or hand in the stats of an earlier call).  Q [n_q_rows][ldq], K [n_kv_rows][ldkv]; segs: wb::AttnSeg[n_rows]; heads: int32.
+struct WbkAlign {
+  WbkBuf Q, K, segs, heads, stats, M;
+  int64_t ldq, ldkv, n_q_rows, n_kv_rows, n_rows, max_len, n_heads, n_model_heads, ld_stats, ld_row, ldm, filter_width, first,
+      n_total, stages;
+};
+
+int wbk_align(WbkAlign* t) {
+  const int64_t n = t->n_rows, nh = t->n_heads;
+  if (n < 1 || n > 4096 || nh < 1 || nh > 4096 || t->max_len < 1 || t->max_len > wb::ALIGN_MAX_LEN) return WBK_EARG;
+  if (t->ldq % 4 || t->ldkv % 4 || t->ldq < 64 * t->n_model_heads || t->ldkv < 64 * t->n_model_heads) return WBK_EARG;
+  if (!inside(t->Q, 0, t->n_q_rows * t->ldq, 4) || !inside(t->K, 0, t->n_kv_rows * t->ldkv, 4)) return WBK_EARG;
+  if (!aligned16(t->Q, 0, 4) || !aligned16(t->K, 0, 4)) return WBK_EARG;
+  const wb::AttnSeg* sg = (const wb::AttnSeg*)t->segs.host;
+  const int32_t* hd = (const int32_t*)t->heads.host;
+  if (!sg || t->segs.off || t->segs.bytes < n * (int64_t)sizeof(wb::AttnSeg) || !hd || t->heads.off || t->heads.bytes < nh * 4)
+    return WBK_EARG;
+  for (int64_t h = 0; h < nh; h++) if (hd[h] < 0 || hd[h] >= t->n_model_heads) return WBK_EARG;
+  int64_t max_C = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (sg[i].q_len < 1 || sg[i].q_len > t->max_len || sg[i].kv_len < 1 || sg[i].q_row0 < 0 || sg[i].kv_row0 < 0 ||
+        sg[i].q_row0 + (int64_t)sg[i].q_len > t->n_q_rows || sg[i].kv_row0 + (int64_t)sg[i].kv_len > t->n_kv_rows)
+      return WBK_EARG;
+    if (sg[i].q_len > t->ld_stats || sg[i].q_len > t->ld_row || sg[i].kv_len > t->ldm) return WBK_EARG;
+    max_C = std::max<int64_t>(max_C, sg[i].kv_len);
+  }
+  if (!inside(t->stats, 0, nh * n * t->ld_stats * 2, 4) || ((t->stats.off) & 7)) return WBK_EARG;
+  if ((t->stages & 2) && !inside(t->M, 0, n * t->ld_row * t->ldm, 4)) return WBK_EARG;
+  if ((t->stages & 2) && (t->filter_width < 1 || t->filter_width > 15 || !(t->filter_width & 1))) return WBK_EARG;
+  Pool P;
+  char *dQ = upload(P, t->Q), *dK = upload(P, t->K), *dS = upload(P, t->segs), *dH = upload(P, t->heads),
+       *dst = upload(P, t->stats), *dM = upload(P, t->M);
+  if (P.err) return P.err;
+  int status = 0;
+  if (t->stages & 1)
+    wb::launch_align_row_stats(nullptr, (const float*)(dQ + t->Q.off), (int)t->ldq, (const float*)(dK + t->K.off), (int)t->ldkv,
+                               (const wb::AttnSeg*)dS, (int)n, (int)t->max_len, (const int32_t*)dH, (int)nh,
+                               (float2*)(dst + t->stats.off), (int)t->ld_stats);
+  if (t->stages & 2)
+    status = wb::launch_align_accumulate(nullptr, (const float*)(dQ + t->Q.off), (int)t->ldq, (const float*)(dK + t->K.off),
+                                         (int)t->ldkv, (const wb::AttnSeg*)dS, (int)n, (int)t->max_len, (int)max_C,
+                                         (const int32_t*)dH, (int)nh, (const float2*)(dst + t->stats.off), (int)t->ld_stats,
+                                         (float*)(dM + t->M.off), (int)t->ld_row, (int)t->ldm, (int)t->filter_width,
+                                         (int)t->first, (int)t->n_total);
+  status = finish(P, status);
+  if (status < -999) return status;
+  download(P, t->stats, dst); download(P, t->M, dM);
+  return P.err ? P.err : status;
+}
+
+// launch_align_dtw over one matrix X [N][ldx] (negate: X = -M); out [N]
+struct WbkDtw { WbkBuf X, out; int64_t N, C, ldx, negate; };
+
+int wbk_align_dtw(WbkDtw* t) {
+  const int64_t N = t->N, C = t->C;
+  if (N < 1 || C < 1 || C > (1 << 20) || t->ldx < C || !inside(t->X, 0, (N - 1) * t->ldx + C, 4) || !inside(t->out, 0, N, 4))
+    return WBK_EARG;
+  Pool P;
+  char *dX = upload(P, t->X), *dout = upload(P, t->out);
+  const int64_t ldt = (C + 3) / 4;
+  const wb::DtwSeg seg{0, (int32_t)N, (int32_t)C, 0};
+  void *dseg = nullptr, *dtr = nullptr;
+  if (P.ok(hipMalloc(&dseg, sizeof(seg)))) { P.dev.push_back(dseg); P.ok(hipMemcpy(dseg, &seg, sizeof(seg), hipMemcpyHostToDevice)); }
+  if (P.ok(hipMalloc(&dtr, (size_t)(N * ldt * 4)))) P.dev.push_back(dtr);
+  if (P.err) return P.err;
+  int status = wb::launch_align_dtw(nullptr, (const float*)(dX + t->X.off), (int)t->ldx, (int)t->negate, (const wb::DtwSeg*)dseg,
+                                    1, (int)N, (uint32_t*)dtr, N * ldt, (int)ldt, (int32_t*)(dout + t->out.off));
+  status = finish(P, status);
+  if (status < -999) return status;
+  download(P, t->out, dout);
+  return P.err ? P.err : status;
+}
+
 const char* wbk_version() { return "whisper_hip kernel test harness 1"; }
 
 }  // extern "C"

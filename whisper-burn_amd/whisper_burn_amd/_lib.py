@@ -115,6 +115,17 @@ SIGNATURES = {
                                         c_int64_p, c_int64_p]),
     "wb_stitch_windows": (C.c_int, [c_int32_p, C.c_int32, c_int32_p, C.c_int, C.c_int, C.c_int, c_int32_p,
                                     C.c_int64, c_int64_p]),
+    "wb_align_tokens": (C.c_int, [C.c_void_p, c_int32_p, C.c_int, C.c_int, c_int32_p, c_float_p, C.c_int, c_int32_p,
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_float_p]),
+    "wb_session_align": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_int32, c_int32_p, c_float_p]),
+    "wb_dtw_start_positions": (C.c_int, [C.c_int, c_float_p, C.c_int32, C.c_int32, c_int32_p]),
+    "wb_waveform_to_token_times": (C.c_int, [C.c_void_p, c_float_p, C.c_int64, C.c_int, C.POINTER(WbDecodeParams),
+                                             c_uint8_p, C.c_int, C.c_int, c_int32_p, C.c_int32, c_int32_p,
+                                             c_int32_p, C.c_int64, c_int64_p, c_int32_p, C.c_int32, C.c_int32,
+                                             c_float_p, c_float_p]),
+    "wb_stitch_windows_times": (C.c_int, [c_int32_p, C.c_int32, c_int32_p, C.c_int, C.c_int, C.c_int, c_int32_p,
+                                          C.c_int64, c_int64_p, c_float_p, c_float_p]),
     "wb_first_repetition_end": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_repetition_period": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_find_repeated_tokens_index": (C.c_int, [c_int32_p, C.c_int64, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),

@@ -39,6 +39,37 @@ def _ip(a: np.ndarray):
     return a.ctypes.data_as(_lib.c_int32_p)
 
 
+def _heads_arg(heads):
+    """(layer, head) pairs -> (int32 array or None, count) for the alignment entry points (None: the default set)."""
+    if heads is None:
+        return None, 0
+    h = _i32(np.asarray(heads, dtype=np.int32).reshape(-1, 2))
+    return h, len(h)
+
+
+def _rows_arg(tokens, lens):
+    """token rows (a 2-D array + lens, or a list of rows of different lengths) -> (int32 [n, L], int32 [n])."""
+    if lens is None and not isinstance(tokens, np.ndarray):
+        rows = [list(r) for r in tokens]
+        lens = [len(r) for r in rows]
+        L = max(lens)
+        tokens = np.zeros((len(rows), L), dtype=np.int32)
+        for i, r in enumerate(rows):
+            tokens[i, :len(r)] = r
+    tokens = _i32(tokens)
+    lens = _i32(lens if lens is not None else [tokens.shape[1]] * tokens.shape[0])
+    return tokens, lens
+
+
+def dtw_start_positions(x, device: int = 0) -> np.ndarray:
+    """DTW (device) over a cost matrix x [N, C] f32: the column of the first path cell of every row."""
+    x = _f32(x)
+    N, Cc = x.shape
+    out = np.zeros(N, dtype=np.int32)
+    check(_lib.load().wb_dtw_start_positions(device, _fp(x), N, Cc, _ip(out)))
+    return out
+
+
 def special_mask_bytes(whisper: "Whisper", is_special) -> np.ndarray:
     """uint8 [n_vocab] for the C side, which reads exactly n_vocab bytes.  The reference adds a [vocab_size] mask to
     [.., n_vocab] logits (transcribe.rs:243-275) and panics when the tokenizer's vocabulary and the model's differ; a
@@ -294,6 +325,23 @@ class Whisper:
         check(_lib.load().wb_forward_decoder(self._h, _ip(tokens), n, L, _fp(enc), enc.shape[1], _fp(logits)))
         return logits
 
+    def align_tokens(self, tokens, encoder_output, lens=None, heads=None, n_prefix: int = 4, drop_last: int = 1,
+                     filter_width: int = 7, return_matrix: bool = False):
+        """Token start positions from the cross-attention weights (wb_align_tokens): tokens [n, L] (+ lens) or a list
+        of rows, encoder_output [n, C, d] -> start_pos [n, L] (-1 where a token is not aligned) and, on request, the
+        token x position matrix [n, L, C].  heads: (layer, head) pairs; None = the upper half of the decoder."""
+        tokens, lens = _rows_arg(tokens, lens)
+        enc = _f32(encoder_output)
+        n, L = tokens.shape
+        assert enc.shape[0] == n and enc.shape[2] == self.dims["n_text_state"]
+        h, nh = _heads_arg(heads)
+        pos = np.full((n, L), -1, dtype=np.int32)
+        mat = np.zeros((n, L, enc.shape[1]), dtype=np.float32) if return_matrix else None
+        check(_lib.load().wb_align_tokens(self._h, _ip(tokens), n, L, _ip(lens), _fp(enc), enc.shape[1],
+                                          _ip(h) if h is not None else None, nh, n_prefix, drop_last, filter_width,
+                                          _ip(pos), _fp(mat) if mat is not None else None))
+        return (pos, mat) if return_matrix else pos
+
     def forward(self, mel, tokens) -> np.ndarray:
         mel = _f32(mel)
         tokens = _i32(tokens)
@@ -337,12 +385,21 @@ def find_chunk_overlap(prev_tokens: Sequence[int], curr_tokens: Sequence[int], m
 
 
 def stitch_windows(win_tokens: np.ndarray, win_lens: np.ndarray, max_n_offsets: int = 40,
-                   min_n_overlaps: int = 3) -> List[int]:
-    """Fold transcribe.rs:56-63 over per-window token rows in window order."""
+                   min_n_overlaps: int = 3, times: Optional[np.ndarray] = None):
+    """Fold transcribe.rs:56-63 over per-window token rows in window order.  With `times` (a float per token, same
+    shape as win_tokens) returns (tokens, times): a stitched token keeps the value of the window it was taken from."""
     wt, wl = _i32(win_tokens), _i32(win_lens)
     cap = int(wl.sum()) + 1
     out = np.zeros(cap, dtype=np.int32)
     n_out = C.c_int64(0)
+    if times is not None:
+        tm = _f32(times)
+        assert tm.shape == wt.shape
+        out_t = np.zeros(cap, dtype=np.float32)
+        check(_lib.load().wb_stitch_windows_times(_ip(wt), wt.shape[1] if wt.ndim == 2 else 0, _ip(wl), len(wl),
+                                                  max_n_offsets, min_n_overlaps, _ip(out), cap, C.byref(n_out),
+                                                  _fp(tm), _fp(out_t)))
+        return out[:n_out.value].tolist(), out_t[:n_out.value].copy()
     check(_lib.load().wb_stitch_windows(_ip(wt), wt.shape[1] if wt.ndim == 2 else 0, _ip(wl), len(wl),
                                         max_n_offsets, min_n_overlaps, _ip(out), cap, C.byref(n_out)))
     return out[:n_out.value].tolist()
@@ -387,6 +444,40 @@ def waveform_to_tokens(whisper: Whisper, st: SpecialTokens, waveform, sample_rat
                                             C.byref(n_st)))
     per_window = [win_tokens[i, :win_lens[i]].tolist() for i in range(n_local)]
     return stitched[:n_st.value].tolist(), per_window
+
+
+def waveform_to_token_times(whisper: Whisper, st: SpecialTokens, waveform, sample_rate: int = 16000,
+                            beam_size: int = 5, max_depth: int = 100, params: Optional[WbDecodeParams] = None,
+                            heads=None, filter_width: int = 7):
+    """waveform_to_tokens + token start times (wb_waveform_to_token_times).
+
+    Returns (stitched tokens, stitched times [s], per-window token lists, per-window time arrays); a time is NaN for
+    the prompt tokens and a final <|endoftext|> of the window the token came from."""
+    lib = _lib.load()
+    wav = _f32(waveform).reshape(-1)
+    p = params or decode_params(st, beam_size, max_depth)
+    wlen = max_waveform_samples(whisper.max_mel_frames() - p.padding)
+    starts, _ = window_extents(len(wav), sample_rate, wlen, p.overlap_seconds)
+    n_win = max(len(starts), 1)
+    stride = 4 + p.max_depth + 4
+    win_tokens = np.zeros((n_win, stride), dtype=np.int32)
+    win_lens = np.zeros(n_win, dtype=np.int32)
+    win_times = np.full((n_win, stride), np.nan, dtype=np.float32)
+    cap = n_win * stride
+    stitched = np.zeros(cap, dtype=np.int32)
+    stitched_t = np.full(cap, np.nan, dtype=np.float32)
+    n_st = C.c_int64(0)
+    mask = special_mask_bytes(whisper, st.is_special)
+    h, nh = _heads_arg(heads)
+    check(lib.wb_waveform_to_token_times(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p),
+                                         mask.ctypes.data_as(_lib.c_uint8_p), 0, -1, _ip(win_tokens), stride,
+                                         _ip(win_lens), _ip(stitched), cap, C.byref(n_st),
+                                         _ip(h) if h is not None else None, nh, filter_width, _fp(win_times),
+                                         _fp(stitched_t)))
+    n = len(starts)
+    return (stitched[:n_st.value].tolist(), stitched_t[:n_st.value].copy(),
+            [win_tokens[i, :win_lens[i]].tolist() for i in range(n)],
+            [win_times[i, :win_lens[i]].copy() for i in range(n)])
 
 
 def waveform_to_text(whisper: Whisper, bpe, lang, waveform, sample_rate: int = 16000):
@@ -461,6 +552,28 @@ class Session:
         lens = np.zeros(self.n_windows, dtype=np.int32)
         check(_lib.load().wb_session_decode(self._h, C.byref(params), _ip(toks), stride, _ip(lens)))
         return [toks[i, :lens[i]].tolist() for i in range(self.n_windows)]
+
+    def align(self, tokens, lens=None, heads=None, n_prefix: int = 4, drop_last: int = 1, filter_width: int = 7,
+              return_matrix: bool = False):
+        """Token start positions of one row per window (wb_session_align), on the session's encoder output and cached
+        cross-attention K: start_pos [W, L] (-1 where a token is not aligned) and, on request, the matrix [W, L, maxC]."""
+        tokens, lens = _rows_arg(tokens, lens)
+        W, L = tokens.shape
+        assert W == self.n_windows
+        h, nh = _heads_arg(heads)
+        pos = np.full((W, L), -1, dtype=np.int32)
+        mat = None
+        if return_matrix:
+            c = C.c_int32(0)
+            maxC = 0
+            for w in range(W):
+                check(_lib.load().wb_session_encoder_output(self._h, w, None, C.byref(c)))
+                maxC = max(maxC, c.value)
+            mat = np.zeros((W, L, maxC), dtype=np.float32)
+        check(_lib.load().wb_session_align(self._h, _ip(tokens), L, _ip(lens), _ip(h) if h is not None else None, nh,
+                                           n_prefix, drop_last, filter_width, _ip(pos),
+                                           _fp(mat) if mat is not None else None))
+        return (pos, mat) if return_matrix else pos
 
     def close(self):
         if self._h:

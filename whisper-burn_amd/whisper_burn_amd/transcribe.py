@@ -9,6 +9,10 @@ written to `<transcription file>` (main.rs:151-154).  Exit code 1 with the refer
 `--frontend reference` after the four positional arguments computes the log-mel with the reference's own recipe
 (dense f32 DFT, wb_model_set_frontend) instead of the default exact-twiddle FFT.
 
+`--token-times PATH` additionally writes one JSON object per line for every stitched non-special token:
+`{"id", "text", "start"}` with the token's start time in seconds (2 decimals), from the decoder's cross-attention
+alignment (wb_waveform_to_token_times).  Without the flag the output is what it always was.
+
 One addition: with `WHISPER_HIP_RESAMPLE=1` in the environment a mono WAV of another sample rate (the bundled
 22 050 Hz audio.wav, which the reference sends through `sox`, README.md:69-74) is resampled to 16 kHz on the GPU
 (wb_resample_dev) instead of being rejected.
@@ -30,13 +34,22 @@ def main(argv=None) -> int:
         return 1
     model_name, wav_file, lang, text_file = argv[1:5]
     frontend = None
+    times_file = None
     extra = argv[5:]
-    if extra and extra[0] == "--frontend":      # (other trailing arguments are ignored, as before)
-        if len(extra) < 2 or extra[1] not in ("fft", "reference"):
-            print(f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference]",
-                  file=sys.stderr)
-            return 1
-        frontend = extra[1]
+    usage = (f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference] "
+             f"[--token-times PATH]")
+    while extra:                                # (other trailing arguments are ignored, as before)
+        if extra[0] in ("--frontend", "--token-times"):
+            if len(extra) < 2 or (extra[0] == "--frontend" and extra[1] not in ("fft", "reference")):
+                print(usage, file=sys.stderr)
+                return 1
+            if extra[0] == "--frontend":
+                frontend = extra[1]
+            else:
+                times_file = extra[1]
+            extra = extra[2:]
+        else:
+            extra = extra[1:]
     if lang not in LANGUAGES:
         print(f"Invalid language abbreviation: {lang}", file=sys.stderr)
         return 1
@@ -79,8 +92,14 @@ def main(argv=None) -> int:
         def decode(self, tokens, skip_special):
             return bpe.decode(tokens, skip_special)
 
+    token_times = None
     try:
-        text, _tokens = wb.waveform_to_text(whisper, Bpe(), lang, waveform, sample_rate)
+        if times_file is None:
+            text, _tokens = wb.waveform_to_text(whisper, Bpe(), lang, waveform, sample_rate)
+        else:
+            st = bpe.special_tokens(lang)
+            _tokens, token_times, _, _ = wb.waveform_to_token_times(whisper, st, waveform, sample_rate)
+            text = bpe.decode(_tokens, True)
     except Exception as e:                                                 # noqa: BLE001
         print(f"Error during transcription: {e}", file=sys.stderr)
         return 1
@@ -90,6 +109,18 @@ def main(argv=None) -> int:
     except OSError as e:
         print(f"Error writing transcription file: {e}", file=sys.stderr)
         return 1
+    if times_file is not None:
+        import json
+        import math
+        try:
+            with open(times_file, "w") as fh:
+                for tok, t in zip(_tokens, token_times):
+                    if st.is_special[tok] or math.isnan(t):
+                        continue
+                    fh.write(json.dumps({"id": int(tok), "text": bpe.decode([tok], True), "start": round(float(t), 2)}) + "\n")
+        except OSError as e:
+            print(f"Error writing token times file: {e}", file=sys.stderr)
+            return 1
     print("Transcription finished.")
     return 0
 
