@@ -1,5 +1,5 @@
 // C ABI of libwhisper_hip.so: model handles and the stateless, reference-shaped entry points.
-// (The stateful session / decode driver entry points live in session.cpp / transcribe.cpp.)
+// (The stateful session / decode driver entry points live in session.cpp / decode_step.cpp / transcribe.cpp.)
 #include <cstring>
 #include <mutex>
 

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "switches.h"
 #include "wave_ops.h"
 
 namespace wb {
@@ -567,10 +568,6 @@ __global__ __launch_bounds__(NW * 64) void attention_f16x3_kernel(const float* _
 
 }  // namespace
 
-static bool attention_kvsplit_enabled() {
-  static const bool on = [] { const char* e = getenv("WHISPER_HIP_ATTN_KVSPLIT"); return !(e && e[0] == '0'); }();
-  return on;
-}
 
 // split: the 16-bit matrix path (attention_f16x3_kernel) for the LDS-tiled shapes; the key-split kernel for small grids and the
 // 64-query blocks stay exact f32
@@ -578,11 +575,10 @@ bool launch_attention(hipStream_t st, const float* Q, int ldq, const float* K, c
                       float* O, int ldo, const AttnSeg* segs_dev, int n_segs, int max_q_len, int n_head,
                       float scale, int causal, bool split, uint16_t* Oh, uint16_t* Ol) {
   if (n_segs <= 0 || max_q_len <= 0) return false;
-  static const bool f16_enabled = [] { const char* e = getenv("WHISPER_HIP_ATTN_F16"); return !(e && e[0] == '0'); }();
   // (tests/kernel_cases.py attn_branch mirrors this choice and the ladder of launch_attention_f32 below)
   const int64_t blocks128 = (int64_t)((max_q_len + 127) / 128) * n_head * n_segs;
-  const bool kvsplit = !causal && max_q_len >= 256 && blocks128 < 384 && attention_kvsplit_enabled();
-  if (split && f16_enabled && !kvsplit && max_q_len > 64) {
+  const bool kvsplit = !causal && max_q_len >= 256 && blocks128 < 384 && sw::attn_kvsplit();
+  if (split && sw::attn_f16() && !kvsplit && max_q_len > 64) {
     dim3 grid((max_q_len + 127) / 128, n_head, n_segs);
     const bool pieces = Oh != nullptr && Ol != nullptr;
     hipLaunchKernelGGL((attention_f16x3_kernel<4>), grid, dim3(256), 0, st, Q, ldq, K, V, ldkv, O, ldo, segs_dev,
@@ -598,7 +594,7 @@ void launch_attention_f32(hipStream_t st, const float* Q, int ldq, const float* 
                           float scale, int causal) {
   if (n_segs <= 0 || max_q_len <= 0) return;
   const int64_t blocks128 = (int64_t)((max_q_len + 127) / 128) * n_head * n_segs;
-  if (!causal && max_q_len >= 256 && blocks128 < 384 && attention_kvsplit_enabled()) {
+  if (!causal && max_q_len >= 256 && blocks128 < 384 && sw::attn_kvsplit()) {
     // a few windows: 128-query blocks cannot fill 256 CUs; split the keys over the waves instead
     dim3 grid((max_q_len + 31) / 32, n_head, n_segs);
     hipLaunchKernelGGL((attention_f32_kvsplit_kernel<4>), grid, dim3(256), 0, st, Q, ldq, K, V, ldkv, O, ldo, segs_dev,

@@ -38,6 +38,7 @@
 #include "decode.h"
 #include "handoff.h"
 #include "kernels.h"
+#include "switches.h"
 #include "wave_ops.h"
 
 namespace wb {
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(SK_NT, MT <= 2 ? 2 : 1) void dec_skinny_f16x3_kerne
     }
   }
   // range guard (an activation left fp16's range: inf / NaN): the host fails the decode call and switches the model to the
-  // exact-f32 kernel above (session.cpp: dec_split_check)
+  // exact-f32 kernel above (decode_step.cpp: dec_split_check)
   if (bad && a.range_flag) __hip_atomic_fetch_or(a.range_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256) void split_weight_f16_tiles_kernel(const float
 // (profiles/r03_l_layer_cycle_large_v2.txt).  0: the shape is not served (the caller keeps the tiled GEMM)
 int skinny_ksplit(int K, int N, int max_ks, int max_rows) {
   if (N % 64 != 0 || K % 32 != 0) return 0;
-  static const int max_blocks = []() { const char* e = getenv("WHISPER_HIP_SK_MAX_BLOCKS"); return e ? atoi(e) : 256; }();
+  const int max_blocks = sw::sk_max_blocks();
   const int strips = N / 64;
   int best = 0;
   const int nt = K / 32;
@@ -376,7 +377,7 @@ int launch_dec_skinny_gemm(hipStream_t st, const SkinnyArgs& a) {
     }
     return 0;
   }
-  static const bool pair = []() { const char* e = getenv("WHISPER_HIP_SK_PAIR"); return e && e[0] == '1'; }();
+  const bool pair = sw::sk_pair();
 #define WB_SK(MT_)                                                                              \
   do {                                                                                          \
     if (pair) WB_KLAUNCH((dec_skinny_gemm_kernel<MT_, true>), grid, block, 0, st, a);            \

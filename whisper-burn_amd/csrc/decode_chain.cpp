@@ -1,0 +1,475 @@
+// Device-chained greedy decode: the persistent flag-chained launch (decode_persist.hip) and the graph-replayed chain of one
+// launch per sublayer behind it.
+#include <climits>
+#include <cstring>
+
+#include "decode_step.h"
+#include "handoff.h"
+#include "switches.h"
+
+using namespace wb;
+
+namespace wb {
+
+// The whole chained greedy decode as ONE persistent launch (decode_persist.hip): every sublayer of every step runs in a
+// co-resident grid whose blocks hand their output planes to each other through arrival counters.  Enqueues the first
+// step's prepare kernel, the control block and the launch, then waits for the stream.  *steps_done = steps executed.
+//
+// *fell_back: the launch was refused (no cooperative launch on this device / partition, the grid not co-resident, a
+// second cooperative client) or a wait gave up before ANY step was committed -- the caller re-seeds the control block and
+// runs the graph-replayed chain of one launch per sublayer instead (it derives everything from gctl), and the session
+// stops trying the persistent kernel.  A wait that gives up after steps were committed stays an error.
+static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_until_len, const int32_t* forced, int n_forced,
+                                int* steps_done, bool* fell_back) {
+  *fell_back = false;
+  WB_REQUIRE(n_forced >= 0 && n_forced <= PS_MAX_FORCED, WB_ERR_ARG, "persistent decode: %d prompt steps", n_forced);
+  // test hook (tests/test_emu_functional.py, tests/test_gpu_switches.py): "launch" = behave as if the cooperative launch was refused
+  const char* inject = sw::persist_inject_fail();
+  wb_model* m = s->m;
+  const wb_dims& D = m->dims;
+  const int d = D.n_text_state, H = D.n_text_head, NL = D.n_text_layer, V = D.n_vocab, S = s->S, W = s->W;
+  const StepLayout& L = s->lay;
+  hipStream_t st = s->st;
+  const int NB = dec_mlp_fused_planes(d);
+  const int n_tiles = (V + 127) / 128;
+  const size_t pool = (size_t)s->Lmax * S;
+  const int ldkv = 2 * d;
+  // ---- the hand-off buffers: residual streams and partial planes as {tag, value} granules (zero-filled once: tag 0 is
+  // never used; the tags of a launch live above launch_count << 16, so leftovers of earlier decodes never match)
+  WB_REQUIRE(NB <= 32 && H <= 8, WB_ERR_SHAPE, "persistent decode: more planes than its folds hold");
+  WB_TRY(s->ps_gx.ensure_zeroed(((size_t)2 * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gpa.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gpc.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gp2.ensure_zeroed(((size_t)NB * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gxn.ensure_zeroed(((size_t)S + 8) * d * 8, st));
+  if (((s->ps_launches + 1) & 0xffffu) == 0) {     // the 16-bit launch count wraps: forget every old tag
+    for (DevMem* b : {&s->ps_gx, &s->ps_gpa, &s->ps_gpc, &s->ps_gp2, &s->ps_gxn}) WB_HIP(hipMemsetAsync(b->p, 0, b->bytes, st));
+    s->ps_launches++;
+  }
+  const unsigned tag_base = ((++s->ps_launches) & 0xffffu) << 16;
+  char* gxb[2] = {static_cast<char*>(s->ps_gx.p), static_cast<char*>(s->ps_gx.p) + (size_t)S * d * 8};
+  // ---- per-layer arguments: exactly what enqueue_step hands the fused sublayer kernels ----
+  std::vector<PsLayerArgs> la(NL);
+  float* xb[2] = {s->x.as<float>(), s->x.as<float>() + (size_t)S * d};
+  int xi = 0;
+  for (int l = 0; l < NL; l++) {
+    const DecBlockW& b = m->dec[l];
+    AttnFusedArgs& fa = la[l].attn;
+    fa.st = s->state.as<int>(); fa.lay = L; fa.S = S; fa.d = d; fa.n_head = H;
+    fa.x_in = xb[xi]; fa.pend = l == 0 ? nullptr : s->P2.as<float>(); fa.KSp = l == 0 ? 0 : NB;
+    fa.pbias = l == 0 ? nullptr : m->dec[l - 1].mlp2.b; fa.x_out = xb[xi ^ 1];
+    fa.ln_g = b.ln1.g; fa.ln_b = b.ln1.b; fa.ln_eps = b.ln1.eps; fa.ln_inside = m->ln_eps_inside_sqrt;
+    fa.Wqkv = b.qkv.w; fa.ldqkv = b.qkv.n; fa.bqkv = b.qkv.b; fa.scale = m->qk_scale;
+    fa.Kc = s->kc.as<float>() + (size_t)l * pool * d; fa.Vc = s->vc.as<float>() + (size_t)l * pool * d;
+    fa.tabs = s->tabs.as<int>(); fa.Lmax = s->Lmax; fa.Wo = b.out.w; fa.P = s->Pa.as<float>();
+    fa.g_x_in = gxb[xi]; fa.g_pend = l == 0 ? nullptr : s->ps_gp2.p; fa.g_x_out = gxb[xi ^ 1]; fa.g_P = s->ps_gpa.p;
+    xi ^= 1;
+    CrossFusedArgs& ca = la[l].cross;
+    ca.st = s->state.as<int>(); ca.lay = L; ca.S = S; ca.d = d; ca.n_head = H;
+    ca.x_in = xb[xi]; ca.pend = s->Pa.as<float>(); ca.KSp = H; ca.pbias = b.out.b; ca.x_out = xb[xi ^ 1];
+    ca.ln_g = b.ln2.g; ca.ln_b = b.ln2.b; ca.ln_eps = b.ln2.eps; ca.ln_inside = m->ln_eps_inside_sqrt;
+    ca.Wq = b.cq.w; ca.bq = b.cq.b; ca.scale = m->qk_scale;
+    ca.ckv = s->ckv.as<float>() + (size_t)l * s->enc_rows * 2 * d; ca.ldkv = ldkv; ca.koff = 0;   // layer-major cached K|V
+    ca.win_row0 = s->win_meta.as<int>(); ca.win_C = s->win_meta.as<int>() + W;
+    ca.Wo = b.cout.w; ca.P = s->Pc.as<float>();
+    ca.n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;
+    ca.g_x_in = gxb[xi]; ca.g_pend = s->ps_gpa.p; ca.g_x_out = gxb[xi ^ 1]; ca.g_P = s->ps_gpc.p;
+    xi ^= 1;
+    MlpFusedArgs& ma = la[l].mlp;
+    ma.st = s->state.as<int>(); ma.S = S; ma.d = d;
+    ma.x_in = xb[xi]; ma.pend = s->Pc.as<float>(); ma.KSp = H; ma.pbias = b.cout.b; ma.x_out = xb[xi ^ 1];
+    ma.ln_g = b.ln3.g; ma.ln_b = b.ln3.b; ma.ln_eps = b.ln3.eps; ma.ln_inside = m->ln_eps_inside_sqrt;
+    ma.W1 = b.mlp1.w; ma.ld1 = b.mlp1.n; ma.b1 = b.mlp1.b; ma.W2 = b.mlp2.w; ma.P = s->P2.as<float>();
+    ma.g_x_in = gxb[xi]; ma.g_pend = s->ps_gpc.p; ma.g_x_out = gxb[xi ^ 1]; ma.g_P = s->ps_gp2.p;
+    xi ^= 1;
+  }
+  // ---- one step's roles, dealt to the blocks: every block runs its own list, in dependency order, every step ----
+  std::vector<PsRole> lr;                            // the layer roles in dependency order
+  for (int l = 0; l < NL; l++) {
+    for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_ATTN, l, h, r});
+    for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_CROSS, l, h, r});
+    for (int j = 0; j < NB; j++) lr.push_back(PsRole{PSR_MLP, l, j, 0});
+  }
+  const int grid = std::max(1, std::min(s->ps_grid, (int)lr.size() + n_tiles + 2 * W));
+  std::vector<std::vector<PsRole>> deal(grid);
+  for (size_t i = 0; i < lr.size(); i++) deal[i % grid].push_back(lr[i]);
+  // logits: blocks that hold a first-layer attention role stay free of it -- they are the first to be needed in the next
+  // step and should be back at their wait (weights requested) before this one ends.  Every logits block takes a run of
+  // consecutive 128-column tiles behind ONE fold + LayerNorm.
+  std::vector<int> cand;
+  for (int b = 0; b < grid; b++) {
+    bool early = false;
+    for (const PsRole& r : deal[b]) early |= r.layer == 0 && (r.kind == PSR_ATTN || r.kind == PSR_CROSS);
+    if (!early) cand.push_back(b);
+  }
+  if ((int)cand.size() * 4 < n_tiles) { cand.clear(); for (int b = 0; b < grid; b++) cand.push_back(b); }
+  // final LayerNorm (one per row): blocks without any layer role if there are some (they sit between the last MLP and
+  // the logits on the critical path), else the least loaded ones; they take no logits work
+  std::vector<char> is_fin(grid, 0);
+  {
+    std::vector<int> order(grid);
+    for (int b = 0; b < grid; b++) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
+    for (int r = 0; r < W; r++) { deal[order[r % grid]].push_back(PsRole{PSR_FINLN, 0, 0, r}); is_fin[order[r % grid]] = 1; }
+  }
+  if ((int)cand.size() > 2 * W) cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int b) { return is_fin[b] != 0; }), cand.end());
+  std::stable_sort(cand.begin(), cand.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
+  const int tpb = (n_tiles + (int)cand.size() - 1) / (int)cand.size();
+  const int n_lg = (n_tiles + tpb - 1) / tpb;
+  for (int q = 0; q < n_lg; q++)
+    deal[cand[q]].push_back(PsRole{PSR_LOGITS, q, q * tpb, std::min(tpb, n_tiles - q * tpb)});
+  // merge (one per row): the least loaded blocks
+  {
+    std::vector<int> order(grid);
+    for (int b = 0; b < grid; b++) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
+    for (int r = 0; r < W; r++) deal[order[r % grid]].push_back(PsRole{PSR_MERGE, 0, 0, r});
+  }
+  std::vector<PsRole> roles;
+  std::vector<int> role_off(grid + 1, 0);
+  for (int b = 0; b < grid; b++) {
+    role_off[b] = (int)roles.size();
+    roles.insert(roles.end(), deal[b].begin(), deal[b].end());
+  }
+  role_off[grid] = (int)roles.size();
+  const int n_ctl = ps_ctl_ints(S, NL);
+  WB_TRY(s->ps_layers.ensure(la.size() * sizeof(PsLayerArgs)));
+  WB_TRY(s->ps_roles.ensure(roles.size() * sizeof(PsRole) + role_off.size() * 4));
+  WB_TRY(s->ps_ctl.ensure((size_t)n_ctl * 4));
+  WB_TRY(s->ps_dead.ensure((size_t)S * 4));
+  WB_TRY(s->ps_tstats.ensure((size_t)S * n_tiles * 2 * 4));
+  std::vector<int> ctl0(n_ctl, 0);
+  ctl0[HX_STOP] = INT_MAX;
+  WB_HIP(hipMemcpyAsync(s->ps_layers.p, la.data(), la.size() * sizeof(PsLayerArgs), hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemcpyAsync(s->ps_roles.p, roles.data(), roles.size() * sizeof(PsRole), hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemcpyAsync(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole), role_off.data(), role_off.size() * 4,
+                        hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemcpyAsync(s->ps_ctl.p, ctl0.data(), (size_t)n_ctl * 4, hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemsetAsync(s->ps_dead.p, 0, (size_t)S * 4, st));
+  PersistArgs a;
+  a.layers = s->ps_layers.as<PsLayerArgs>(); a.roles = s->ps_roles.as<PsRole>(); a.n_roles = (int)roles.size();
+  a.role_off = reinterpret_cast<const int*>(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole));
+  a.n_logits_roles = n_lg;
+  a.n_layer = NL; a.n_rows = W; a.S = S; a.d = d; a.n_head = H; a.nb_mlp = NB;
+  a.n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;
+  a.ctl = s->ps_ctl.as<int>(); a.step0 = s->step; a.n_steps = n_forced + max_depth; a.mask_until_len = mask_until_len;
+  a.n_forced = n_forced;
+  for (int i = 0; i < n_forced; i++) a.forced[i] = forced[i];
+  a.g_xn = s->ps_gxn.p;
+  a.x_fin = gxb[xi]; a.P2 = s->ps_gp2.p; a.b2_last = m->dec[NL - 1].mlp2.b; a.tag_base = tag_base;
+  a.ln_g = m->ln_dec.g; a.ln_b = m->ln_dec.b; a.ln_eps = m->ln_dec.eps; a.ln_inside = m->ln_eps_inside_sqrt;
+  a.Et = m->tok_emb_t; a.vocab_ld = m->vocab_ld; a.V = V; a.mask = s->mask.as<float>();
+  a.tstats = s->ps_tstats.as<float>(); a.n_tiles = n_tiles;
+  a.gctl = s->gctl.as<int>(); a.gtok = s->gtok.as<int>(); a.Lmax = s->Lmax; a.eot = eot;
+  a.E = m->tok_emb; a.pos = m->dec_pos; a.x0 = gxb[0]; a.tabs = s->tabs.as<int>(); a.dead = s->ps_dead.as<int>();
+  // optional role timeline (developer): WHISPER_HIP_PS_STAMPS=<file> dumps [n_steps][n_roles][3] 100 MHz clock values
+  const char* stamps_path = sw::ps_stamps();
+  const size_t n_stamps = stamps_path ? (size_t)(n_forced + max_depth) * roles.size() * 8 : 0;
+  if (n_stamps) {
+    WB_TRY(s->ps_stamps.ensure(n_stamps * 8));
+    WB_HIP(hipMemsetAsync(s->ps_stamps.p, 0, n_stamps * 8, st));
+    a.stamps = s->ps_stamps.as<unsigned long long>();
+  }
+  WB_REQUIRE(3 * NL * (n_forced + max_depth + 1) + 4 < 0x10000, WB_ERR_SHAPE,
+             "persistent decode: %d layers x %d steps do not fit the 16-bit granule tags", NL, max_depth);
+  // first step of the chain: token + position embedding of the last prompt token (every later step: the merge role)
+  launch_dec_prepare(st, reinterpret_cast<const int*>(s->host_block_dev), s->state.as<int>(), L, W, s->tabs.as<int>(),
+                     s->Lmax, m->tok_emb, m->dec_pos, d, s->x.as<float>(), s->gctl.as<int>());
+  launch_ps_seed(st, s->x.as<float>(), W * d, gxb[0], tag_base + 1u);
+  WB_HIP(hipStreamSynchronize(st));            // (the staging vectors above are on the stack)
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  prof_tag(KC_PERSIST, 0.0);                   // (its necessary bytes are known when the rows' lengths are: added by the caller)
+  const bool timed = prof_take_events(&e0, &e1);
+  if (timed) WB_HIP(hipEventRecord(e0, st));
+  const bool refused = (inject && !strcmp(inject, "launch")) || launch_dec_persist(st, a, grid) != 0;
+  if (timed) WB_HIP(hipEventRecord(e1, st));
+  if (refused) {
+    (void)hipGetLastError();                   // (clears the sticky launch error)
+    s->ps_grid = 0;
+    *fell_back = true;
+    *steps_done = 0;
+    return WB_OK;
+  }
+  std::vector<int> ctl(n_ctl);
+  WB_HIP(hipMemcpyAsync(ctl.data(), s->ps_ctl.p, (size_t)n_ctl * 4, hipMemcpyDeviceToHost, st));
+  int gstep = 0;
+  WB_HIP(hipMemcpyAsync(&gstep, s->gctl.as<int>() + GC_STEP, 4, hipMemcpyDeviceToHost, st));
+  WB_HIP(hipStreamSynchronize(st));
+  if (ctl[HX_ERR] != 0 && gstep == s->step) {  // nothing committed: the chain can take over from the same control block
+    s->ps_grid = 0;
+    *fell_back = true;
+    *steps_done = 0;
+    return WB_OK;
+  }
+  WB_REQUIRE(ctl[HX_ERR] == 0, WB_ERR_HIP, "persistent decode: a wait gave up (counter %d) at step %d", ctl[HX_ERR] - 1, gstep);
+  if (n_stamps) {
+    std::vector<unsigned long long> hs(n_stamps);
+    WB_HIP(hipMemcpy(hs.data(), s->ps_stamps.p, n_stamps * 8, hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(stamps_path, "wb")) {
+      const int hdr[4] = {n_forced + max_depth, (int)roles.size(), grid, 8};
+      fwrite(hdr, 4, 4, f);
+      std::vector<int> kinds(roles.size());
+      for (size_t i = 0; i < roles.size(); i++)
+        kinds[i] = roles[i].kind | ((roles[i].kind <= PSR_MLP ? roles[i].layer : 0) << 8) |
+                   ((roles[i].kind == PSR_LOGITS ? 0 : roles[i].b) << 16);
+      fwrite(kinds.data(), 4, kinds.size(), f);
+      fwrite(hs.data(), 8, hs.size(), f);
+      fclose(f);
+    }
+  }
+  *steps_done = std::max(0, std::min(n_forced + max_depth, gstep - s->step));
+  return WB_OK;
+}
+
+// Device-chained greedy decode (beam_size == 1): after the host-driven prompt prefill, every step's
+// argmax is fed to the next step on the device; the host only replays the step graph and checks the
+// per-window finished flags every `chunk` steps.  Equivalent to beam.rs with k = 1: the single beam is
+// extended by its best continuation (lowest id on ties) until it ends in EOT or max_depth tokens.
+// A fresh session (step 0) hands in the whole prompt: the persistent kernel runs the prompt's first prompt_len - 1 positions as
+// forced steps of the same launch (no host round trip between the prompt and the first generated token); the chain of one
+// launch per sublayer (and the persistent kernel's fallback) prefills through host-driven steps first, as before.
+int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_depth, int mask_until_len, int prompt_len,
+                         int32_t* out_tokens, int32_t row_stride, int32_t* out_lens) {
+  wb_model* m = s->m;
+  const int S = s->S, W = s->W;
+  WB_REQUIRE(S == W, WB_ERR_STATE, "chained greedy decode needs max_beams == 1");
+  WB_REQUIRE(prompt && prompt_len >= 1, WB_ERR_ARG, "chained greedy decode: empty prompt");
+  WB_REQUIRE(s->step == 0 || (s->prev_n == W && s->step == prompt_len - 1), WB_ERR_STATE,
+             "chained greedy decode: the session is neither fresh nor prefilled");
+  const int n_forced_max = prompt_len - 1;          // prompt positions that can run inside the persistent launch
+  auto host_prefill = [&]() -> int {                 // transcribe.rs:203: the prompt, one KV-cached step per token, no logits
+    std::vector<int32_t> tok(W), par(W), win(W);
+    for (int t = s->step; t < prompt_len - 1; t++) {
+      for (int w = 0; w < W; w++) { tok[w] = prompt[t]; par[w] = t == 0 ? -1 : w; win[w] = w; }
+      WB_TRY(wb_session_step(s, tok.data(), par.data(), win.data(), W, 0, 0, nullptr, nullptr));
+    }
+    return WB_OK;
+  };
+  // the first steps read the special-token mask (transcribe.rs:271-275): same contract as wb_session_step
+  WB_REQUIRE(s->has_mask || mask_until_len < prompt_len || max_depth == 0, WB_ERR_STATE,
+             "wb_session_decode: special mask not set");
+  // The reference only fails (mod.rs:134-139) when a sequence actually outgrows n_text_ctx: a large max_depth
+  // whose windows all end on EOT earlier succeeds.  Run at most the steps the context holds; raise the
+  // reference's error afterwards if a window is still unfinished.
+  const int asked_depth = max_depth;
+  max_depth = std::min(max_depth, s->Lmax - (prompt_len - 1));
+  WB_HIP(hipSetDevice(m->device));
+  hipStream_t st = s->st;
+  const size_t ctl_ints = GC_HDR + 3 * (size_t)S;
+  WB_TRY(s->gctl.ensure(ctl_ints * 4));
+  // token rows [S][Lmax]; the last generated token of a row that fills the context lands at index Lmax
+  // (= slot 0 of the next row, a prompt position nobody reads), so the buffer carries one extra slot
+  WB_TRY(s->gtok.ensure(((size_t)S * s->Lmax + 1) * 4));
+  std::vector<int> ctl(ctl_ints, 0);
+  auto seed_ctl = [&]() -> int {                     // the chain starts at the session's step with that position's prompt token
+    std::fill(ctl.begin(), ctl.end(), 0);
+    ctl[GC_STEP] = s->step;
+    for (int i = 0; i < W; i++) ctl[GC_HDR + i] = prompt[s->step];
+    WB_HIP(hipMemcpyAsync(s->gctl.p, ctl.data(), ctl_ints * 4, hipMemcpyHostToDevice, st));
+    WB_HIP(hipStreamSynchronize(st));
+    return WB_OK;
+  };
+  const StepPlan plan = plan_step(s, W, false);     // (no 9 - 16-row fused bucket here: W in 9..16 is batch mode)
+  const int n_launch = plan.n_launch;
+  const bool fuse_ln = plan.fuse_ln;
+  const int chunk = 16;
+  int depth = 0;                                   // steps enqueued so far
+  bool persist = plan.persist && max_depth > 0;
+  if (persist) {
+    if (s->ps_grid < 0) s->ps_grid = dec_persist_max_grid(m->device, m->dims.n_text_state, W, s->maxC);
+    persist = s->ps_grid > 0;
+  }
+  // prompt positions the persistent launch runs itself (a fresh session; WHISPER_HIP_PERSIST_PREFILL=0: host-driven prefill)
+  int n_forced = 0;
+  if (persist && sw::persist_prefill() && s->step == 0 && n_forced_max <= PS_MAX_FORCED && s->has_mask) n_forced = n_forced_max;
+  if (n_forced == 0) WB_TRY(host_prefill());
+  WB_TRY(seed_ctl());
+  ScopedTimer tm(st, 3);
+  if (persist) {
+    bool fell_back = false;
+    WB_TRY(run_persistent_chain(s, eot, max_depth, mask_until_len, prompt + s->step + 1, n_forced, &depth, &fell_back));
+    if (fell_back) {
+      // rows whose merge role ran before the give-up have moved their control words: prefill on the host (if the launch was
+      // to do it) and start the chain over from the seed
+      persist = false;
+      depth = 0;
+      WB_TRY(host_prefill());
+      WB_TRY(seed_ctl());
+      n_forced = 0;
+    } else {
+      if (profile().on) profile().ms[4] += depth;
+      depth -= n_forced;                             // from here on `depth` counts GENERATED positions
+      s->step += n_forced;
+      s->prev_n = W;
+      s->prev_win.resize(W);
+      for (int w = 0; w < W; w++) s->prev_win[w] = w;
+    }
+  }
+  if (!persist) {
+  if (fuse_ln)   // first step of the chain; every later one is prepared by its predecessor's merge kernel
+    launch_dec_prepare(st, reinterpret_cast<const int*>(s->host_block_dev), s->state.as<int>(), s->lay, n_launch,
+                       s->tabs.as<int>(), s->Lmax, m->tok_emb, m->dec_pos, m->dims.n_text_state, s->x.as<float>(),
+                       s->gctl.as<int>());
+  // masked steps (the first two, transcribe.rs:271-275) and the tail shorter than a chunk go one step per
+  // graph launch; in between, a whole chunk of steps is ONE graph launch (two multi-step shapes are never
+  // needed: only {1 step masked, 1 step, chunk steps} are captured).
+  //
+  // Small batches (the fused-LayerNorm path) run one segment AHEAD of the finished flags: segment k + 1 is enqueued
+  // before the flags of segment k are read (on a second stream, behind an event), so the GPU never idles across
+  // the host round trip (~60-400 us per check in round 1's timeline).  If every window turns out to be finished,
+  // the merge kernel has already blanked the step state (ST_N = 0) and the kernels of the speculative segment exit
+  // at their first instruction.  Batch mode (> 8 rows: MFMA GEMMs that do not look at ST_N) keeps the blocking check.
+  // (opt-in: measured 1417x vs 1543x -- a graph launched behind a running graph starts later than one launched on an
+  // idle stream saves)
+  const bool speculate = fuse_ln && sw::speculate();
+  if (speculate && !s->st2) {
+    WB_HIP(hipStreamCreateWithFlags(&s->st2, hipStreamNonBlocking));
+    WB_HIP(hipEventCreateWithFlags(&s->ev_seg, hipEventDisableTiming));
+  }
+  auto enqueue_segment = [&](int* enq) -> int {   // >= `chunk` steps (or what is left); returns steps enqueued via *enq
+    int n = 0;
+    while (depth + n < max_depth && n < chunk) {
+      const int d0 = depth + n;
+      const int use_mask = (prompt_len + d0) <= mask_until_len ? 1 : 0;
+      const int run = (!use_mask && max_depth - d0 >= chunk) ? chunk : 1;
+      StepCall call;
+      call.k = 1; call.use_mask = use_mask; call.chained = true; call.eot = eot; call.reps = run;
+      WB_TRY(launch_step(s, plan, call));
+      if (profile().on) profile().ms[4] += run;
+      n += run;
+    }
+    *enq = n;
+    return WB_OK;
+  };
+  auto read_flags = [&](bool behind_event) -> int {
+    if (behind_event) {
+      WB_HIP(hipStreamWaitEvent(s->st2, s->ev_seg, 0));
+      WB_HIP(hipMemcpyAsync(ctl.data(), s->gctl.p, ctl_ints * 4, hipMemcpyDeviceToHost, s->st2));
+      WB_HIP(hipStreamSynchronize(s->st2));
+    } else {
+      WB_HIP(hipMemcpyAsync(ctl.data(), s->gctl.p, ctl_ints * 4, hipMemcpyDeviceToHost, st));
+      WB_HIP(hipStreamSynchronize(st));
+    }
+    return WB_OK;
+  };
+  auto all_done = [&]() {
+    bool d = true;
+    for (int i = 0; i < W; i++) d = d && ctl[GC_HDR + S + i] != 0;
+    return d;
+  };
+  // small batches: the merge kernel publishes (steps completed, finished) per row into mapped host memory; the host
+  // spins on it (a few us) instead of a D2H copy + stream synchronisation (30-190 us of idle GPU per check in round 1)
+  const bool poll = fuse_ln && sw::poll() && !profile().on;
+  volatile int* hfl = reinterpret_cast<volatile int*>(s->host_block + s->chain_flags_off);
+  if (poll) for (int i = 0; i < 2 * S; i++) hfl[i] = 0;
+  auto wait_flags = [&](int want_step, bool* done) -> int {
+    for (long spins = 0;; spins++) {
+      bool ready = true;
+      for (int i = 0; i < W && ready; i++) ready = hfl[2 * i] >= want_step;
+      if (ready) break;
+      bool fin = true;
+      for (int i = 0; i < W && fin; i++) fin = hfl[2 * i + 1] != 0;
+      if (fin) break;                              // every window finished: the rest of the chunk is blanked
+      if ((spins & 0xfff) == 0xfff) {             // every 4096 spins: is the stream still alive / busy?
+        const hipError_t q = hipStreamQuery(st);
+        if (q == hipSuccess) {                     // stream drained: the flags are final (or the chain ended early)
+          bool r2 = true;
+          for (int i = 0; i < W && r2; i++) r2 = hfl[2 * i] >= want_step;
+          if (r2) break;
+          bool all = true;
+          for (int i = 0; i < W; i++) all = all && hfl[2 * i + 1] != 0;
+          if (all) break;                          // every window finished: later steps were blanked
+          set_error("chained decode: the device stopped at step %d of %d", (int)hfl[0], want_step);
+          return WB_ERR_HIP;
+        }
+        if (q != hipErrorNotReady) { set_error("chained decode: %s", hipGetErrorString(q)); return WB_ERR_HIP; }
+      }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    bool all = true;
+    for (int i = 0; i < W; i++) all = all && hfl[2 * i + 1] != 0;
+    *done = all;
+    return WB_OK;
+  };
+  if (!speculate) {
+    while (depth < max_depth) {
+      int n = 0;
+      WB_TRY(enqueue_segment(&n));
+      depth += n;
+      if (poll) {
+        bool done = false;
+        WB_TRY(wait_flags(s->step + depth, &done));
+        if (done) break;
+      } else {
+        WB_TRY(read_flags(false));
+        if (all_done()) break;
+      }
+    }
+  } else {
+    int n_cur = 0;
+    WB_TRY(enqueue_segment(&n_cur));
+    depth += n_cur;
+    while (true) {
+      WB_HIP(hipEventRecord(s->ev_seg, st));        // end of the segment whose flags are read next
+      int n_next = 0;
+      if (depth < max_depth) { WB_TRY(enqueue_segment(&n_next)); depth += n_next; }
+      WB_TRY(read_flags(true));
+      if (all_done() || n_next == 0) break;
+    }
+    WB_HIP(hipStreamSynchronize(st));
+  }
+  }   // (!persist)
+  tm.stop();
+  std::vector<int> toks((size_t)S * s->Lmax + 1);
+  WB_HIP(hipMemcpyAsync(ctl.data(), s->gctl.p, ctl_ints * 4, hipMemcpyDeviceToHost, st));
+  WB_HIP(hipMemcpyAsync(toks.data(), s->gtok.p, toks.size() * 4, hipMemcpyDeviceToHost, st));
+  WB_HIP(hipStreamSynchronize(st));
+  tm.collect();
+  WB_TRY(dec_split_check(s));
+  WB_REQUIRE(ctl[GC_BAD] == 0, WB_ERR_STATE, "a decode step produced a row without a finite log-prob (NaN logits: non-finite "
+             "weights or activations); its window was ended on <|endoftext|> on the device and the rows of this call are invalid");
+  for (int w = 0; w < W; w++) {
+    int len = ctl[GC_HDR + 2 * S + w];                 // prompt + generated (through EOT if it came)
+    if (len < prompt_len) len = prompt_len;
+    len = std::min(len, prompt_len + max_depth);
+    WB_REQUIRE(len <= row_stride, WB_ERR_ARG, "row_stride too small");
+    for (int p = prompt_len; p < len; p++) out_tokens[(size_t)w * row_stride + p] = toks[(size_t)w * s->Lmax + p];
+    out_lens[w] = len;
+  }
+  if (profile().on && !persist && s->prof_cls_cross >= 0 && s->prof_cls_self >= 0) {
+    // The tags counted every launched row's cached K/V.  A row whose window had already ended is marked dead in the
+    // step state: its attention blocks exit at their first wait and stream nothing -- take those bytes back, so that
+    // the reported algorithmic bytes are the NECESSARY ones.
+    const int dm = m->dims.n_text_state, NL = m->dims.n_text_layer;
+    double dead_ckv = 0, dead_self = 0;
+    for (int w = 0; w < W; w++) {
+      const int live = std::max(0, std::min(out_lens[w] - prompt_len, depth));   // steps in which row w was live
+      for (int t = live; t < depth; t++) { dead_ckv += 8.0 * s->C[w] * dm; dead_self += 8.0 * (s->step + t + 1) * dm; }
+    }
+    prof_adjust_bytes(s->prof_cls_cross, -(double)NL * dead_ckv);
+    prof_adjust_bytes(s->prof_cls_self, -(double)NL * dead_self);
+  }
+  if (profile().on && persist) {
+    // necessary bytes of the persistent launch: weights + E^T once per executed step, a row's cached cross K/V and
+    // self-attention rows only while its window is live
+    const double dm = m->dims.n_text_state, NL = m->dims.n_text_layer;
+    double bytes = (double)(depth + n_forced) * 4.0 * NL * 14.0 * dm * dm + (double)depth * 4.0 * (double)m->dims.n_vocab * dm;
+    for (int w = 0; w < W; w++)                      // (the prompt positions the launch ran itself: every row is live there)
+      for (int t = 0; t < n_forced; t++) bytes += NL * (8.0 * s->C[w] * dm + 8.0 * (t + 1) * dm);
+    for (int w = 0; w < W; w++) {
+      const int live = std::max(0, std::min(out_lens[w] - prompt_len, depth));
+      for (int t = 0; t < live; t++) bytes += NL * (8.0 * s->C[w] * dm + 8.0 * (s->step + t + 1) * dm);
+    }
+    prof_adjust_bytes(KC_PERSIST, bytes);
+  }
+  s->prof_step_off = 0;
+  s->step += depth;
+  s->prev_len.assign(W, s->step);
+  s->last_had_logits = 0;
+  if (max_depth < asked_depth)
+    for (int w = 0; w < W; w++)
+      WB_REQUIRE(ctl[GC_HDR + S + w] != 0, WB_ERR_SHAPE, "Token sequence length %d must not exceed %d.", s->Lmax + 1,
+                 s->Lmax);
+  return WB_OK;
+}
+}  // namespace wb

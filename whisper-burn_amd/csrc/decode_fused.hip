@@ -19,6 +19,7 @@
 
 #include "decode.h"
 #include "decode_fused_bodies.h"
+#include "switches.h"
 #include "wave_ops.h"
 
 namespace wb {
@@ -192,8 +193,7 @@ int dec_mlp_fused_planes(int d) { return 4 * d / 64; }
 
 void launch_dec_mlp_fused(hipStream_t st, const MlpFusedArgs& a, int n_rows_hint) {
   // 9 - 16 rows with plain planes: one pass on the matrix cores (WHISPER_HIP_MLP16_MFMA=0: two row groups of 8 on the vector pipe)
-  static const bool mfma16 = []() { const char* e = getenv("WHISPER_HIP_MLP16_MFMA"); return !(e && e[0] == '0'); }();
-  if (mfma16 && n_rows_hint > 8 && n_rows_hint <= 16 && a.n_chunks == 0 && a.row0 == 0) {
+  if (sw::mlp16_mfma() && n_rows_hint > 8 && n_rows_hint <= 16 && a.n_chunks == 0 && a.row0 == 0) {
     const dim3 grid16(4 * a.d / 64), block16(512);
     if (a.d == 128) WB_KLAUNCH((dec_mlp16_mfma_kernel<2>), grid16, block16, 0, st, a);
     else if (a.d == 384) WB_KLAUNCH((dec_mlp16_mfma_kernel<6>), grid16, block16, 0, st, a);

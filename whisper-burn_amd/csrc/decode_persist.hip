@@ -14,7 +14,7 @@
 //   per layer l: attn (head h, row r) x H R  ->  cross (h, r) x H R  ->  mlp (64-unit hidden slice j) x 4 d / 64
 //   final LN (row r) x R: ln(x + last MLP planes), once per row   ->   logits (a run of 128-column vocabulary tiles)
 //   ->   merge (row r) x R
-// The host deals the roles to the blocks (session.cpp): a block runs its own list, in dependency order, every step.  The
+// The host deals the roles to the blocks (decode_chain.cpp): a block runs its own list, in dependency order, every step.  The
 // first sublayers' blocks take no logits work (they are back at their wait, weights requested, before the step ends).
 // Dependencies = arrival counters (handoff.h), monotonic within the launch:
 //   attn(0,.,r)  waits for merge(r) of the previous step (its x row)          c_x[r]       >= e

@@ -1,6 +1,7 @@
 // Encoder / decoder forward passes: the reference's module graph (src/model/mod.rs) expressed as a
 // short sequence of fused gfx950 launches over packed, ragged window batches.
 #include "engine.h"
+#include "switches.h"
 
 #include <sys/syscall.h>
 #include <unistd.h>
@@ -14,8 +15,7 @@ namespace wb {
 
 GpuTurn::GpuTurn(int device) {
   static std::recursive_mutex mu[64];          // (per device: the fault is a co-execution fault of one GPU's SIMDs)
-  static const bool enabled = []() { const char* e = getenv("WHISPER_HIP_GPU_TURN"); return !(e && e[0] == '0'); }();
-  if (enabled) lk = std::unique_lock<std::recursive_mutex>(mu[device < 0 ? 0 : device & 63]);
+  if (sw::gpu_turn()) lk = std::unique_lock<std::recursive_mutex>(mu[device < 0 ? 0 : device & 63]);
 }
 
 int get_mel_tables(int device, double sample_rate, const MelTables** out_dev) {
@@ -107,7 +107,7 @@ void launch_mel_frontend(hipStream_t st, const MelFrontend& fe, const float* pcm
 namespace {
 struct EncTrace { std::vector<std::string> name; std::vector<DevMem> buf; std::vector<size_t> bytes; size_t n = 0; };
 thread_local EncTrace tl_trace;
-const char* enc_trace_dir() { static const char* d = getenv("WHISPER_HIP_ENC_TRACE"); return d; }
+const char* enc_trace_dir() { return sw::enc_trace(); }
 void trace_stage(hipStream_t st, const std::string& name, const void* p, size_t bytes) {
   if (!enc_trace_dir()) return;
   EncTrace& t = tl_trace;
@@ -342,14 +342,13 @@ int run_encoder_unguarded(wb_model* m, hipStream_t st, Workspace& ws, const MelB
   // LayerNorm, the attention kernel, the GELU epilogue of lin1 -- write them as fp16 hi / lo planes once (the same 4 bytes per
   // element, in the same buffers), and the GEMM's A path is two 16-byte loads straight to LDS.  WHISPER_HIP_ENCODER_PIECES=0
   // keeps f32 activations (every column block of every consumer then splits its A tile itself, as in round 5).
-  static const bool pieces_enabled = []() { const char* e = getenv("WHISPER_HIP_ENCODER_PIECES"); return !(e && e[0] == '0'); }();
   const bool split_pass = m->split_active() && tl_split_flag != nullptr && d % 32 == 0;
   uint16_t* h_hi = reinterpret_cast<uint16_t*>(h); uint16_t* h_lo = h_hi + (size_t)rows2 * d;
   uint16_t* att_hi = reinterpret_cast<uint16_t*>(att); uint16_t* att_lo = att_hi + (size_t)rows2 * d;
   uint16_t* hm_hi = reinterpret_cast<uint16_t*>(hm); uint16_t* hm_lo = hm_hi + (size_t)rows2 * 4 * d;
   for (int i = 0; i < D.n_audio_layer; i++) {   // ResidualEncoderAttentionBlock::forward, mod.rs:299-303
     const EncBlockW& b = m->enc[i];
-    const bool pcs = pieces_enabled && split_pass && b.qkv.sh && b.out.sh && b.mlp1.sh && b.mlp2.sh;
+    const bool pcs = sw::encoder_pieces() && split_pass && b.qkv.sh && b.out.sh && b.mlp1.sh && b.mlp2.sh;
     GemmArgs g = linear_args(h, rows2, b.qkv, qkv);
     if (pcs) {
       launch_layernorm_pieces(st, x, h_hi, h_lo, rows2, d, b.ln1.g, b.ln1.b, b.ln1.eps, m->ln_eps_inside_sqrt);

@@ -24,6 +24,7 @@
 #include <utility>
 
 #include "kernels.h"
+#include "switches.h"
 
 namespace wb {
 namespace {
@@ -349,7 +350,7 @@ int launch_gemm_f16x3(hipStream_t st, const GemmArgs& a, const uint16_t* Wh, con
   if (a.Ch && (!a.Cl || a.ksplit > 1 || a.c_block_cols > 0)) return -1;
   if (a.ksplit > 1 && (a.bias || a.residual || a.aux || a.act != ACT_NONE || a.col_scale_period > 0)) return -1;
   auto blocks = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-  static const int force_tile = []() { const char* e = getenv("WHISPER_HIP_SPLIT_TILE"); return e ? atoi(e) : 0; }();   // developer A/B
+  const int force_tile = sw::split_tile();   // developer A/B
   // (measured in round 5 and not kept: 128 x 64 tiles with three / four k-tiles in flight -- half the accumulators buy the
   // registers for a deeper queue -- large-v2 encoder 226 / 225 ms against 195.6 for 128 x 128 with one: the large shapes are not
   // bound by bytes in flight; the extra operand traffic and A-split work per flop cost more: profiles/r05_i_k12_tiles.txt)

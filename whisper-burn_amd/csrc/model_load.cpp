@@ -13,6 +13,7 @@
 #include "wb_internal.h"
 #include "kernels.h"
 #include "decode.h"
+#include "switches.h"
 
 namespace wb { void session_pool_register(wb_model* m); }
 
@@ -382,8 +383,7 @@ int build_model(TensorMap& tm, int device, int compute_dtype, wb_model** out) {
   // ---- fp16 hi / lo copies of the encoder-side GEMM weights for the three-product kernel
   // (gemm_f16x3.hip: f32-grade results at ~2x the rate of the exact-f32 MFMA); made on the device, once.
   // WHISPER_HIP_ENCODER_SPLIT=0 keeps the exact-f32 MFMA kernel for everything.
-  static const bool split_enabled = []() { const char* e = getenv("WHISPER_HIP_ENCODER_SPLIT"); return e ? e[0] == '1' : WB_ENCODER_SPLIT_DEFAULT; }();
-  if (split_enabled) {
+  if (sw::encoder_split()) {
     std::vector<LinearW*> cand, ws;
     for (int i = 0; i < D.n_audio_layer; i++) {
       cand.push_back(&m->enc[i].qkv); cand.push_back(&m->enc[i].out); cand.push_back(&m->enc[i].mlp1); cand.push_back(&m->enc[i].mlp2);
@@ -419,8 +419,7 @@ int build_model(TensorMap& tm, int device, int compute_dtype, wb_model** out) {
   // dec_skinny_f16x3_kernel: the decoder's weight stream on the 16-bit matrix path, f32-grade results).  The f32 copies stay:
   // the <= 8-row kernels (fused sublayers, persistent decode) and the stateless decoder use them.
   // WHISPER_HIP_DECODER_SPLIT=0 keeps the exact-f32 skinny kernel.
-  static const bool dec_split_enabled = []() { const char* e = getenv("WHISPER_HIP_DECODER_SPLIT"); return !(e && e[0] == '0'); }();
-  if (dec_split_enabled && compute_dtype == WB_F32) {
+  if (sw::decoder_split() && compute_dtype == WB_F32) {
     std::vector<LinearW*> ws;
     const float* arena_dev = m->arena.as<float>();
     for (int i = 0; i < D.n_text_layer; i++)

@@ -63,7 +63,7 @@ struct wb_session {
 };
 
 namespace wb {
-// profile accumulators (session.cpp)
+// profile accumulators (profile.cpp)
 struct Profile {
   bool on = false;
   double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};

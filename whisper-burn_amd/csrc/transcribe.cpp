@@ -8,6 +8,7 @@
 
 #include "engine.h"
 #include "session.h"
+#include "switches.h"
 
 using namespace wb;
 
@@ -296,8 +297,7 @@ extern "C" int wb_session_decode(wb_session* s, const wb_decode_params* p, int32
   WB_REQUIRE(p->beam_size >= 1 && p->beam_size <= s->max_beams, WB_ERR_ARG, "beam_size %d outside [1, %d]",
              p->beam_size, s->max_beams);
   if (!s->decode_ready || s->Lmax < 4 + p->max_depth) WB_TRY(session_reserve(s, 4 + p->max_depth + 1));
-  static const bool chain_enabled = []() { const char* e = getenv("WHISPER_HIP_CHAIN"); return !(e && e[0] == '0'); }();
-  if (p->beam_size == 1 && s->max_beams == 1 && chain_enabled && p->max_depth > 0 && s->step == 0) {
+  if (p->beam_size == 1 && s->max_beams == 1 && sw::chain() && p->max_depth > 0 && s->step == 0) {
     // greedy: prompt prefill through the ordinary step, then the device-chained loop (no per-step host round trip)
     const int V = s->m->dims.n_vocab, W = s->W;
     const int32_t prompt[4] = {p->tok_start_of_transcript, p->tok_language, p->tok_transcribe, p->tok_no_timestamps};
@@ -310,7 +310,7 @@ extern "C" int wb_session_decode(wb_session* s, const wb_decode_params* p, int32
                                 row_stride, out_lens);
   }
   if (s->step == 0) {
-    // beam search with the bookkeeping on the device (session.cpp: session_beam_chain; WHISPER_HIP_BEAM_CHAIN=0: host-driven)
+    // beam search with the bookkeeping on the device (beam_chain.cpp: session_beam_chain; WHISPER_HIP_BEAM_CHAIN=0: host-driven)
     const int V = s->m->dims.n_vocab;
     const int32_t prompt[4] = {p->tok_start_of_transcript, p->tok_language, p->tok_transcribe, p->tok_no_timestamps};
     for (int t : prompt) WB_REQUIRE(t >= 0 && t < V, WB_ERR_ARG, "prompt token %d out of range", t);

@@ -136,9 +136,8 @@ struct Workspace {
 }  // namespace wb
 
 // Encoder-side Linear layers of exact-f32 models run on the split-precision kernel (gemm_f16x3.hip) unless
-// WHISPER_HIP_ENCODER_SPLIT=0: as close to the exact result as the f32 MFMA kernel or closer (its K chain is 16 x shorter:
-// profiles/r04_a_diag_*), at about twice the rate.
-constexpr bool WB_ENCODER_SPLIT_DEFAULT = true;
+// WHISPER_HIP_ENCODER_SPLIT=0 (switches.h: encoder_split, on by default): as close to the exact result as the f32 MFMA kernel
+// or closer (its K chain is 16 x shorter: profiles/r04_a_diag_*), at about twice the rate.
 
 struct wb_model {
   // process-unique, never reused (build_model): the session pool and the captured decode graphs are keyed by it, not by
@@ -166,7 +165,7 @@ struct wb_model {
   int* split_flag_host = nullptr; int* split_flag_dev = nullptr; int split_off = 0;
   bool split_active() const { return arena_split.p && !__atomic_load_n(&split_off, __ATOMIC_ACQUIRE); }
   // decoder side (batch-mode skinny GEMM on fp16 hi / lo tiles): its own arena and off switch; the flag words are the
-  // sessions' (guard_host[1]), checked wherever a decode synchronises with the host (session.cpp: dec_split_check): a trip
+  // sessions' (guard_host[1]), checked wherever a decode synchronises with the host (decode_step.cpp: dec_split_check): a trip
   // fails THAT session's call loudly and switches the model to the exact-f32 decoder GEMMs, so the caller's retry succeeds;
   // other sessions drop their captured step graphs the next time they look one up (the graph key carries the switch).
   wb::DevMem arena_dec_split;

@@ -1,6 +1,6 @@
 // Developer probe: encoder self-attention at the bench geometry (3 windows of tiny.en), 128-query blocks vs the
 // key-split variant; prints time and the largest difference between the two.
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/attn_probe.cpp -o tools/attn_probe
+// hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/attn_probe.cpp csrc/switches.cpp -o tools/attn_probe
 #include "../csrc/attention.hip"
 #include <cstdio>
 #include <vector>

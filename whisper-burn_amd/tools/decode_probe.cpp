@@ -1,6 +1,6 @@
 // Developer probe (not part of the library): per-kernel latency of the decode-step kernels at
 // tiny.en geometry, launched back to back, warm vs rotating (cold) weights, eager vs hipGraph.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/decode_probe.cpp csrc/build/decode.hip.o <decode_fused.hip built with -DWB_STAMPS> -o tools/decode_probe
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/decode_probe.cpp csrc/build/decode.hip.o csrc/build/switches.cpp.o <decode_fused.hip built with -DWB_STAMPS> -o tools/decode_probe
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>

@@ -2,7 +2,7 @@
 // (global_load_lds_dwordx4, counted vmcnt, raw barriers, a ring of LDS stages) against the product kernel
 // (gemm_f16x3_kernel<128, 128, 2, 2, 1, APRE = true>) at large-v2's / small's encoder shapes.  Same MFMA order over k ->
 // outputs must be bit-identical.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/gemm_glds_probe.cpp -o tools/gemm_glds_probe
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip tools/gemm_glds_probe.cpp csrc/switches.cpp -o tools/gemm_glds_probe
 #include "../csrc/gemm_f16x3.hip"
 #include <cstdio>
 #include <cstring>
