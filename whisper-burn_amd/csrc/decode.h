@@ -247,6 +247,9 @@ struct PersistArgs {
   const PsLayerArgs* layers = nullptr;        // [n_layer] (device)
   const PsRole* roles = nullptr; int n_roles = 0;   // one step's roles, grouped by block, each block's in dependency order (device)
   const int* role_off = nullptr;              // [grid + 1]: block b runs roles [role_off[b], role_off[b + 1]) every step
+  // [grid]: the index of block b's role that keeps step-invariant operands resident in LDS for the whole launch (the block's
+  // only layer role, a self- or cross-attention one), -1: none.  Null: no block does (WHISPER_HIP_PERSIST_RESIDENT=0)
+  const int* res_role = nullptr;
   int n_logits_roles = 0;
   int n_layer = 0, n_rows = 0, S = 0, d = 0, n_head = 0, nb_mlp = 0;
   int n_pass = 1;                             // key passes of the cross-attention roles (2: a window with > CROSS_FUSED_MAX_C keys)
@@ -271,6 +274,7 @@ struct PersistArgs {
 };
 int ps_ctl_ints(int S, int n_layer);
 bool dec_persist_supported(int d, int n_rows, int max_keys);
+int dec_persist_resident_slots(int d, int n_rows, int max_keys);   // resident float4 slots per thread; 0: nothing useful fits
 // grid: blocks of 512 threads that are co-resident on this device for (d, n_rows) -- 0 if the kernel cannot run
 int dec_persist_max_grid(int device, int d, int n_rows, int max_keys);
 int launch_dec_persist(hipStream_t st, const PersistArgs& a, int grid);

@@ -132,9 +132,25 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
     roles.insert(roles.end(), deal[b].begin(), deal[b].end());
   }
   role_off[grid] = (int)roles.size();
+  // Resident operands (WHISPER_HIP_PERSIST_RESIDENT, default on; "0": off; "log": on, and one line on stderr): a block whose
+  // list holds exactly ONE layer role, a self- or cross-attention one, runs that role every step -- the kernel keeps what
+  // fits of the role's step-invariant operands in the LDS the roles leave free.  Blocks with several layer roles (a grid
+  // smaller than the layer roles) would have to share the region: they run as before.
+  const char* res_sw = sw::persist_resident();
+  const bool res_on = !(res_sw && res_sw[0] == '0') && dec_persist_resident_slots(d, W, s->maxC) > 0;
+  std::vector<int> res_role(grid, -1);              // per block: the index of its resident role
+  int n_res = 0;
+  if (res_on)
+    for (int b = 0; b < grid; b++) {
+      int n_layer_roles = 0, at = -1;
+      for (int i = role_off[b]; i < role_off[b + 1]; i++)
+        if (roles[i].kind <= PSR_MLP) { n_layer_roles++; at = i; }
+      if (n_layer_roles == 1 && roles[at].kind != PSR_MLP) { res_role[b] = at; n_res++; }
+    }
+  if (res_sw && !strcmp(res_sw, "log")) fprintf(stderr, "persist resident blocks: %d of %d\n", n_res, grid);
   const int n_ctl = ps_ctl_ints(S, NL);
   WB_TRY(s->ps_layers.ensure(la.size() * sizeof(PsLayerArgs)));
-  WB_TRY(s->ps_roles.ensure(roles.size() * sizeof(PsRole) + role_off.size() * 4));
+  WB_TRY(s->ps_roles.ensure(roles.size() * sizeof(PsRole) + (role_off.size() + res_role.size()) * 4));
   WB_TRY(s->ps_ctl.ensure((size_t)n_ctl * 4));
   WB_TRY(s->ps_dead.ensure((size_t)S * 4));
   WB_TRY(s->ps_tstats.ensure((size_t)S * n_tiles * 2 * 4));
@@ -142,6 +158,8 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   ctl0[HX_STOP] = INT_MAX;
   WB_HIP(hipMemcpyAsync(s->ps_layers.p, la.data(), la.size() * sizeof(PsLayerArgs), hipMemcpyHostToDevice, st));
   WB_HIP(hipMemcpyAsync(s->ps_roles.p, roles.data(), roles.size() * sizeof(PsRole), hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemcpyAsync(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole) + role_off.size() * 4, res_role.data(),
+                        res_role.size() * 4, hipMemcpyHostToDevice, st));
   WB_HIP(hipMemcpyAsync(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole), role_off.data(), role_off.size() * 4,
                         hipMemcpyHostToDevice, st));
   WB_HIP(hipMemcpyAsync(s->ps_ctl.p, ctl0.data(), (size_t)n_ctl * 4, hipMemcpyHostToDevice, st));
@@ -149,6 +167,7 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   PersistArgs a;
   a.layers = s->ps_layers.as<PsLayerArgs>(); a.roles = s->ps_roles.as<PsRole>(); a.n_roles = (int)roles.size();
   a.role_off = reinterpret_cast<const int*>(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole));
+  if (n_res > 0) a.res_role = a.role_off + role_off.size();
   a.n_logits_roles = n_lg;
   a.n_layer = NL; a.n_rows = W; a.S = S; a.d = d; a.n_head = H; a.nb_mlp = NB;
   a.n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;

@@ -36,17 +36,20 @@ __global__ __launch_bounds__(512) void dec_mlp_fused_kernel(MlpFusedArgs a) {
     a.row0 = r0; a.x_in += sh; a.x_out += sh; a.P += sh;
     if (a.pend) a.pend += sh;
   }
-  dec_mlp_body<MR, DPL, REC, false>(a, blockIdx.x, PsStep());
+  __shared__ MlpLds<MR, DPL, REC> sm;
+  dec_mlp_body<MR, DPL, REC, false>(a, blockIdx.x, PsStep(), sm);
 }
 // grid = (8, rows): workgroups go round-robin over the 8 XCDs by linear id, so x = head puts every beam's block of
 // one head on the SAME XCD -- the head's weight slices cross the fabric once and are shared through that L2
 template <int DPL>
 __global__ __launch_bounds__(512) void dec_attn_fused_kernel(AttnFusedArgs a) {
-  dec_attn_body<DPL, false>(a, blockIdx.x, blockIdx.y, PsStep());
+  __shared__ AttnLds<DPL> sm;
+  dec_attn_body<DPL, false>(a, blockIdx.x, blockIdx.y, PsStep(), sm);
 }
 template <int DPL, int NP>
 __global__ __launch_bounds__(512) void dec_cross_fused_kernel(CrossFusedArgs a) {
-  dec_cross_body<DPL, false, NP>(a, blockIdx.x, blockIdx.y, PsStep());
+  __shared__ CrossLds<DPL, NP> sm;
+  dec_cross_body<DPL, false, NP>(a, blockIdx.x, blockIdx.y, PsStep(), sm);
 }
 
 

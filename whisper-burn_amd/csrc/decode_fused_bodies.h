@@ -83,9 +83,9 @@ __device__ __forceinline__ void ps_nap() {
 
 // developer probe: tools/decode_probe.cpp builds this file with -DWB_STAMPS and prints the phase timeline of block 0
 #ifdef WB_STAMPS
-#define WB_STAMP_DECL __shared__ unsigned long long stamp_buf[16]
-#define WB_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) stamp_buf[i] = wall_clock64(); } while (0)
-#define WB_STAMP_FLUSH(a, n) do { if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && (a).stamps) for (int _i = 0; _i < (n); _i++) (a).stamps[_i] = stamp_buf[_i]; } while (0)
+#define WB_STAMP_DECL unsigned long long stamp_buf[16];             // (a member of the role's LDS struct)
+#define WB_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) sm.stamp_buf[i] = wall_clock64(); } while (0)
+#define WB_STAMP_FLUSH(a, n) do { if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && (a).stamps) for (int _i = 0; _i < (n); _i++) (a).stamps[_i] = sm.stamp_buf[_i]; } while (0)
 #else
 #define WB_STAMP_DECL
 #define WB_STAMP(i) do {} while (0)
@@ -94,6 +94,76 @@ __device__ __forceinline__ void ps_nap() {
 
 constexpr int FD_MAX = 512;      // largest n_state of the fused path (test models 128, tiny.en 384, base.en 512)
 constexpr int FA_MAXPOS = 448;   // n_text_ctx
+
+
+// ---- the roles' LDS ---------------------------------------------------------------------------------------------------
+// Every role body takes the arrays it works in as ONE plain struct.  A one-launch-per-sublayer kernel (decode_fused.hip)
+// declares the struct of its role; the persistent kernel declares one union of all of them (a block runs its roles one after
+// another: their arrays are never live together) and keeps what is left of the CU's 160 KB for operands that do not change
+// from step to step (ResGeom below).
+constexpr int ROLE_NT = 512;     // threads of a role's block
+template <int MR, int DPL, bool REC>
+struct MlpLds {
+  static constexpr int d = 64 * DPL, HS = 64, G = d / 4 <= 32 ? 8 : 4;
+  alignas(16) float hs[MR][d];                     // x + pending, then LN of it
+  alignas(16) float red[8][MR][HS];                // per-wave partial hidden sums
+  alignas(16) float hid[MR][HS];                   // GELU(hidden slice)
+  alignas(16) float obuf[(G - 1) * MR * d];        // phase-2 partials of row groups >= 1
+  float mlb[REC ? MR : 1][48][2];                  // record mode: (m, l) of every (head, chunk)
+  float coef[REC ? MR : 1][48];                    // ... and its flash-combine weight
+  WB_STAMP_DECL
+};
+template <int DPL>
+struct AttnLds {
+  static constexpr int d = 64 * DPL, G = d / 4 <= 32 ? 8 : 4;
+  static constexpr int RED = (8 * 192 > (G - 1) * d) ? 8 * 192 : (G - 1) * d;
+  alignas(16) float hs[d];
+  alignas(16) float red[RED];                      // QKV partials, later the out-projection partials
+  alignas(16) float qkv[192];                      // q * s, k * s, v of the new token (head h)
+  int tbs[FA_MAXPOS];
+  float sc[FA_MAXPOS];
+  alignas(16) float part[32][64];
+  alignas(16) float att[64];
+  WB_STAMP_DECL
+};
+template <int DPL, int NP>
+struct CrossLds {
+  static constexpr int d = 64 * DPL, G = d / 4 <= 32 ? 8 : 4, CMAX = NP * CROSS_FUSED_MAX_C;
+  alignas(16) float hs[d];
+  alignas(16) float red[8][64];
+  alignas(16) float qv[64];
+  float sc[CMAX];
+  float pbuf[CMAX];
+  alignas(16) float part[32][64];
+  alignas(16) float att[64];
+  alignas(16) float obuf[(G - 1) * d];
+};
+
+// ---- resident operands (persistent kernel only) -------------------------------------------------------------------------
+// A block that runs the SAME self- or cross-attention role every step keeps RS float4 per thread of that role's step-invariant
+// operands in LDS for the whole launch: slot s of thread tid lives at res[s * 512 + tid].  A thread reads back only what it
+// wrote itself (no barrier; consecutive lanes sit 16 bytes apart) and every product keeps its operands and its place in the
+// sum, so the bits are those of the streamed path.  What goes in is what the streamed path requests AFTER its wait:
+//   self-attention   QKV weight rounds 2 .. 2 + NRND - 1 (rounds 0 and 1 are in registers before the wait), then NWO_A rows of
+//                    the thread's Wo slice
+//   cross-attention  the V rows of the leading NVT key tiles in the ring's kv[t][i] order (one key pass only: the two-pass
+//                    ring refills its registers with the second pass's K first, and its body is left exactly as it was: it
+//                    sits at the register limit), then NWO_X rows of the Wo slice
+template <int DPL, int NP, int RS>
+struct ResGeom {
+  static constexpr int d = 64 * DPL, G = d / 4 <= 32 ? 8 : 4, RPG = 64 / G;
+  static constexpr int KW = d / 8, RK = DPL >= 6 ? 8 : 16, NIT = KW / RK;         // (dec_attn_body's weight rounds)
+  static constexpr int NRND = (NIT - 2 < RS / RK ? NIT - 2 : RS / RK) > 0 ? (NIT - 2 < RS / RK ? NIT - 2 : RS / RK) : 0;
+  static constexpr int WO_A = NRND * RK;                                           // first Wo slot of the self-attention role
+  static constexpr int NWO_A = RS - WO_A < RPG ? RS - WO_A : RPG;
+  static constexpr int SL = 4, NTILE = CROSS_FUSED_MAX_C / 128;                    // (dec_cross_body's key ring)
+  static constexpr int NVT = NP > 1 ? 0 : (RS / SL < NTILE ? RS / SL : NTILE);
+  static constexpr int WO_X = NVT * SL;
+  static constexpr int NWO_X = NP > 1 ? 0 : (RS - WO_X < RPG ? RS - WO_X : RPG);
+  static_assert(RS >= 0 && WO_A + NWO_A <= RS && WO_X + NWO_X <= RS, "resident slots");
+};
+__device__ __forceinline__ float4 res_ld(const float4* res, int slot, int tid) { return res[slot * ROLE_NT + tid]; }
+__device__ __forceinline__ void res_st(float4* res, int slot, int tid, const float4& v) { res[slot * ROLE_NT + tid] = v; }
 
 __device__ __forceinline__ float gelu_erf_f(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
@@ -244,7 +314,7 @@ __device__ __forceinline__ float lane_get(float v, int src) { return __shfl(v, s
 // rg, rg + 32, ... (d / 32 of them).  Phase 2: thread (cf = tid % (d / 4), jg = tid / (d / 4)) owns a float4 of
 // output columns and 64 / G rows of the W2 slice.
 template <int MR, int DPL, bool REC, bool PS>
-__device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jblk, const PsStep& ps) {
+__device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jblk, const PsStep& ps, MlpLds<MR, DPL, REC>& sm) {
   constexpr int HS = 64, NT = 512;
   constexpr int d = 64 * DPL;
   constexpr int CF = d / 4;
@@ -252,13 +322,8 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
   constexpr int RPG = HS / G;
   constexpr int EPT = (MR * d + NT - 1) / NT;
   constexpr int PCH = EPT <= 3 ? 8 : EPT <= 6 ? 6 : 3;
-  __shared__ __attribute__((aligned(16))) float hs[MR][d];              // x + pending, then LN of it
-  __shared__ __attribute__((aligned(16))) float red[8][MR][HS];         // per-wave partial hidden sums
-  __shared__ __attribute__((aligned(16))) float hid[MR][HS];            // GELU(hidden slice)
-  __shared__ __attribute__((aligned(16))) float obuf[(G - 1) * MR * d]; // phase-2 partials of row groups >= 1
-  __shared__ float mlb[REC ? MR : 1][48][2];                            // record mode: (m, l) of every (head, chunk)
-  __shared__ float coef[REC ? MR : 1][48];                              // ... and its flash-combine weight
-  WB_STAMP_DECL;
+  static_assert(G == MlpLds<MR, DPL, REC>::G, "LDS struct geometry");
+  auto& hs = sm.hs; auto& red = sm.red; auto& hid = sm.hid; auto& obuf = sm.obuf; auto& mlb = sm.mlb; auto& coef = sm.coef;
   WB_STAMP(0);
   const int tid = role_tid<PS>(), lane = tid & 63, wave = tid >> 6;
   const int j0 = jblk * HS;
@@ -604,8 +669,11 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
 // operands + two weight rounds, then (as soon as the position table is known) the cached K / V rows of the first 128
 // positions in the coalesced row layout -- they land under the QKV FMAs; when the weight registers free up: the
 // out-projection slice.  The attention phases and the out-projection do not wait on memory.
-template <int DPL, bool PS>
-__device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int h, const int r, const PsStep& ps) {
+// res (persistent mode): the block's resident operands (ResGeom: RS float4 slots per thread, filled by dec_attn_res_fill at
+// kernel entry), null = everything is streamed.
+template <int DPL, bool PS, int RS = 0>
+__device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int h, const int r, const PsStep& ps, AttnLds<DPL>& sm,
+                                              const float4* res = nullptr) {
   constexpr int NT = 512;
   constexpr int d = 64 * DPL;
   constexpr int KW = d / 8;                        // K rows per wave (16, 48, 64)
@@ -614,16 +682,10 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   constexpr int CF = d / 4;
   constexpr int G = CF <= 32 ? 8 : 4;              // out-projection row groups (d = 128: 8 x 8 rows, 384 / 512: 4 x 16)
   constexpr int RPG = 64 / G;
-  constexpr int RED = (8 * 192 > (G - 1) * d) ? 8 * 192 : (G - 1) * d;
   constexpr int PT = 128, PSL = PT * 16 / NT;      // cached positions per tile, float4 slots per thread per tile (4)
-  __shared__ __attribute__((aligned(16))) float hs[d];
-  __shared__ __attribute__((aligned(16))) float red[RED];              // QKV partials, later the out-projection partials
-  __shared__ __attribute__((aligned(16))) float qkv[192];              // q * s, k * s, v of the new token (head h)
-  __shared__ int tbs[FA_MAXPOS];
-  __shared__ float sc[FA_MAXPOS];
-  __shared__ __attribute__((aligned(16))) float part[32][64];
-  __shared__ __attribute__((aligned(16))) float att[64];
-  WB_STAMP_DECL;
+  using RG = ResGeom<DPL, 1, PS ? RS : 0>;
+  static_assert(G == AttnLds<DPL>::G && RG::RK == RK && RG::NIT == NIT && RG::RPG == RPG && NT == ROLE_NT, "LDS struct / resident geometry");
+  auto& hs = sm.hs; auto& red = sm.red; auto& qkv = sm.qkv; auto& tbs = sm.tbs; auto& sc = sm.sc; auto& part = sm.part; auto& att = sm.att;
   WB_STAMP(0);
   const int tid = role_tid<PS>(), lane = tid & 63, wave = tid >> 6;
   // grid = (8, rows): workgroups go round-robin over the 8 XCDs by linear id, so x = head puts every beam's block of
@@ -790,19 +852,40 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   if constexpr (PS) ps_stamp_fine(ps, 4);
   WB_STAMP(2);
   // ---- QKV for head h (rolled on purpose: unrolled, every round's loads are hoisted to the top and spill)
+  // Resident rounds: rounds 2 .. 2 + nres - 1 come from LDS, between round 1 and the rest; the rounds that still travel
+  // through the registers (the n-th of them is round n for n < 2, else n + nres) are requested into wr[0] / wr[1] as soon as
+  // those are consumed -- in flight under the LDS rounds.  Accumulation order 0, 1, 2, ... either way.
+  const int nres = (RG::NRND > 0 && res != nullptr) ? RG::NRND : 0;
+  const int nreg = NIT - nres;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
-  for (int it = 0; it < NIT; it += 2) {
+  for (int n = 0; n < nreg; n += 2) {
 #pragma unroll
     for (int b = 0; b < 2; b++) {
-      if (it + b < NIT) {
-        const int kb = RK * (it + b);              // (row of the wave's own KW = lane that holds it)
+      if (n + b < nreg) {
+        const int kb = RK * (n + b < 2 ? n + b : n + b + nres);   // (row of the wave's own KW = lane that holds it)
 #pragma unroll
         for (int j = 0; j < RK; j++) {
           const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xn_own), kb + j));
           acc[0] += xv * wr[b][j].x; acc[1] += xv * wr[b][j].y; acc[2] += xv * wr[b][j].z; acc[3] += xv * wr[b][j].w;
         }
-        if (it + b + 2 < NIT) load_round(wr[b], it + b + 2);
+        if (n + b + 2 < nreg) load_round(wr[b], n + b + 2 + nres);
+      }
+      if constexpr (RG::NRND > 0) {
+        if (b == 1 && n == 0 && nres > 0) {
+#pragma unroll 1
+          for (int q = 0; q < RG::NRND; q++) {
+            float4 wl[RK];
+#pragma unroll
+            for (int j = 0; j < RK; j++) wl[j] = res_ld(res, q * RK + j, tid);
+            const int kb = RK * (2 + q);
+#pragma unroll
+            for (int j = 0; j < RK; j++) {
+              const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xn_own), kb + j));
+              acc[0] += xv * wl[j].x; acc[1] += xv * wl[j].y; acc[2] += xv * wl[j].z; acc[3] += xv * wl[j].w;
+            }
+          }
+        }
       }
     }
   }
@@ -816,8 +899,12 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   float4 wo[RPG];
   {
     const float* wp = a.Wo + (int64_t)(h * 64 + jb) * d + cf * 4;
+    if (RG::NWO_A == 0 || res == nullptr) {        // (the resident rows are read from LDS just before their use)
 #pragma unroll
-    for (int i = 0; i < RPG; i++) wo[i] = ld_w4(wp + (int64_t)i * d);
+      for (int i = 0; i < RG::NWO_A; i++) wo[i] = ld_w4(wp + (int64_t)i * d);
+    }
+#pragma unroll
+    for (int i = RG::NWO_A; i < RPG; i++) wo[i] = ld_w4(wp + (int64_t)i * d);
   }
   if (seg_ok) *reinterpret_cast<float4*>(&red[wave * 192 + seg * 64 + c4]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
   __syncthreads();
@@ -919,6 +1006,12 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   WB_STAMP(6);
   if constexpr (PS) ps_stamp(ps, 5);
   // ---- plane h, row r = att Wo[head h rows, :]
+  if constexpr (RG::NWO_A > 0) {
+    if (res != nullptr) {
+#pragma unroll
+      for (int i = 0; i < RG::NWO_A; i++) wo[i] = res_ld(res, RG::WO_A + i, tid);
+    }
+  }
   float ov[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < RPG; i++) {
@@ -955,6 +1048,35 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   return true;
 }
 
+// Fills the self-attention role's resident operands (persistent kernel, once per launch, before the step loop): the same
+// addresses, in the same per-thread order, as dec_attn_body streams them.
+template <int DPL, int RS>
+__device__ __forceinline__ void dec_attn_res_fill(const AttnFusedArgs& a, const int h, float4* res) {
+  using RG = ResGeom<DPL, 1, RS>;
+  constexpr int d = 64 * DPL, KW = d / 8, RK = RG::RK, CF = d / 4, G = RG::G, RPG = RG::RPG;
+  const int tid = role_tid<true>(), lane = tid & 63, wave = tid >> 6;
+  const int seg = lane >> 4, c4 = (lane & 15) * 4;
+  const float* wq = a.Wqkv + (int64_t)(wave * KW) * a.ldqkv + (seg < 3 ? seg : 0) * d + h * 64 + c4;
+#pragma unroll 1
+  for (int q = 0; q < RG::NRND; q++) {
+    float4 w[RK];
+#pragma unroll
+    for (int j = 0; j < RK; j++) w[j] = ld_w4(wq + (int64_t)(RK * (2 + q) + j) * a.ldqkv);
+#pragma unroll
+    for (int j = 0; j < RK; j++) res_st(res, q * RK + j, tid, w[j]);
+  }
+  if constexpr (RG::NWO_A > 0) {
+    const int cf = tid % CF, jg = tid / CF;
+    const int jb = (jg < G ? jg : 0) * RPG;
+    const float* wp = a.Wo + (int64_t)(h * 64 + jb) * d + cf * 4;
+    float4 w[RG::NWO_A];
+#pragma unroll
+    for (int i = 0; i < RG::NWO_A; i++) w[i] = ld_w4(wp + (int64_t)i * d);
+#pragma unroll
+    for (int i = 0; i < RG::NWO_A; i++) res_st(res, RG::WO_A + i, tid, w[i]);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Cross-attention block.  block = 512 threads, grid = (8, rows): block (h, r) owns head h of beam r (x = head keeps a
 // head's blocks on one XCD: the Wq / Wo slices and, for beams of the same window, the cached K/V cross the fabric once).
@@ -975,8 +1097,12 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
 // is done), V of keys [0, 768) (refilled under the second pass of scores), V of keys [768, C) (refilled as the first
 // pass of the output sum consumes a register).  Straight-line code: a window with C <= 768 keys (the tail window) makes
 // the same passes over clamped rows, its scores past C never stored and their probabilities zero.
-template <int DPL, bool PS, int NP = 1>
-__device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const int h, const int r, const PsStep& ps) {
+//
+// res (persistent mode): the block's resident operands (ResGeom; filled by dec_cross_res_fill at kernel entry), null = all
+// streamed.  The registers of a resident tile are not refilled after its scores; the output sum reads its V rows from LDS.
+template <int DPL, bool PS, int NP = 1, int RS = 0>
+__device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const int h, const int r, const PsStep& ps,
+                                               CrossLds<DPL, NP>& sm, const float4* res = nullptr) {
   constexpr int NT = 512;
   constexpr int PASS_C = CROSS_FUSED_MAX_C, CMAX = NP * PASS_C;
   constexpr int d = 64 * DPL;
@@ -986,14 +1112,12 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
   constexpr int RPG = 64 / G;
   constexpr int KT = 128, NTILE = CROSS_FUSED_MAX_C / KT, SL = KT * 16 / NT;   // 6 tiles x 4 float4 slots per thread
   static_assert(CROSS_FUSED_MAX_C % KT == 0 && SL * NT == KT * 16, "tile geometry");
-  __shared__ __attribute__((aligned(16))) float hs[d];
-  __shared__ __attribute__((aligned(16))) float red[8][64];
-  __shared__ __attribute__((aligned(16))) float qv[64];
-  __shared__ float sc[CMAX];
-  __shared__ float pbuf[CMAX];
-  __shared__ __attribute__((aligned(16))) float part[32][64];
-  __shared__ __attribute__((aligned(16))) float att[64];
-  __shared__ __attribute__((aligned(16))) float obuf[(G - 1) * d];
+  using RG = ResGeom<DPL, NP, PS ? RS : 0>;
+  static_assert(G == CrossLds<DPL, NP>::G && CMAX == CrossLds<DPL, NP>::CMAX && RG::SL == SL && RG::NTILE == NTILE && RG::RPG == RPG &&
+                NT == ROLE_NT, "LDS struct / resident geometry");
+  auto& hs = sm.hs; auto& red = sm.red; auto& qv = sm.qv; auto& sc = sm.sc; auto& pbuf = sm.pbuf; auto& part = sm.part; auto& att = sm.att;
+  auto& obuf = sm.obuf;
+  const bool res_v = RG::NVT > 0 && res != nullptr;     // (block-uniform)
   const int tid = role_tid<PS>(), lane = tid & 63, wave = tid >> 6;
   if (h >= a.n_head) return true;
   int n_live, w_row, dead;
@@ -1163,8 +1287,12 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
   float4 wo[RPG];
   {
     const float* wp = a.Wo + (int64_t)(h * 64 + jb) * d + cf * 4;
+    if (RG::NWO_X == 0 || res == nullptr) {        // (the resident rows are read from LDS just before their use)
 #pragma unroll
-    for (int i = 0; i < RPG; i++) wo[i] = ld_w4(wp + (int64_t)i * d);
+      for (int i = 0; i < RG::NWO_X; i++) wo[i] = ld_w4(wp + (int64_t)i * d);
+    }
+#pragma unroll
+    for (int i = RG::NWO_X; i < RPG; i++) wo[i] = ld_w4(wp + (int64_t)i * d);
   }
   if (tid < 64) {
     float v = 0.f;
@@ -1199,7 +1327,8 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
           s += dpp_f<DPP_ROW_MIRROR, 0xF>(0.f, s);
           if ((tid & 15) == 0 && key < C) sc[key] = s;
           const int lim = p + 1 < NP ? max(C - 1 - (p + 1) * PASS_C, -(p + 1) * PASS_C) : C - 1;   // (clamped rows are never consumed)
-          kv[t][i] = gld4(nxt + (min(k0, lim) * a.ldkv + c4));
+          // (a resident tile's V rows stay in LDS: its registers are not refilled)
+          if (t >= RG::NVT || !res_v) kv[t][i] = gld4(nxt + (min(k0, lim) * a.ldkv + c4));
         }
       }
     }
@@ -1231,6 +1360,7 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
         for (int i = 0; i < SL; i++) {
           const int k0 = t * KT + rgp + 32 * i, key = p * PASS_C + k0;
           const float pk = key < C ? pbuf[key] : 0.f;
+          if (t < RG::NVT) { if (res_v) kv[t][i] = res_ld(res, t * SL + i, tid); }
           o.x += pk * kv[t][i].x; o.y += pk * kv[t][i].y; o.z += pk * kv[t][i].z; o.w += pk * kv[t][i].w;
           if (p + 1 < NP)                           // the register takes the V row of the next pass's key
             kv[t][i] = gld4(Vh + (min(key + PASS_C, C - 1) * a.ldkv + c4));
@@ -1249,6 +1379,12 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
   __syncthreads();
   if constexpr (PS) ps_stamp(ps, 5);
   // ---- plane h, row r = att Wo[head h rows, :]
+  if constexpr (RG::NWO_X > 0) {
+    if (res != nullptr) {
+#pragma unroll
+      for (int i = 0; i < RG::NWO_X; i++) wo[i] = res_ld(res, RG::WO_X + i, tid);
+    }
+  }
   float ov[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < RPG; i++) {
@@ -1275,6 +1411,39 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
     else a.x_out[(int64_t)r * d + tid] = xfold;
   }
   return true;
+}
+
+// Fills the cross-attention role's resident operands (persistent kernel, once per launch, before the step loop): the V rows of
+// the row's own window and head, tile by tile in the ring's slot order, then Wo rows -- the addresses dec_cross_body streams.
+// The cached K/V of a window changes from decode to decode: nothing here may outlive the launch.
+template <int DPL, int NP, int RS>
+__device__ __forceinline__ void dec_cross_res_fill(const CrossFusedArgs& a, const int h, const int r, float4* res) {
+  using RG = ResGeom<DPL, NP, RS>;
+  constexpr int d = 64 * DPL, CF = d / 4, G = RG::G, RPG = RG::RPG, KT = 128, SL = RG::SL;
+  const int tid = role_tid<true>();
+  const int rg = tid >> 4, c4 = (tid & 15) * 4;
+  if constexpr (RG::NVT > 0) {
+    const int C = min(gld(a.win_C + r), CROSS_FUSED_MAX_C), row0 = gld(a.win_row0 + r);   // (one beam per window: row == window)
+    const float* Vh = a.ckv + (int64_t)row0 * a.ldkv + a.koff + h * 64 + d;
+#pragma unroll 1
+    for (int t = 0; t < RG::NVT; t++) {
+      float4 v[SL];
+#pragma unroll
+      for (int i = 0; i < SL; i++) v[i] = gld4(Vh + (min(t * KT + rg + 32 * i, C - 1) * a.ldkv + c4));
+#pragma unroll
+      for (int i = 0; i < SL; i++) res_st(res, t * SL + i, tid, v[i]);
+    }
+  }
+  if constexpr (RG::NWO_X > 0) {
+    const int cf = tid % CF, jg = tid / CF;
+    const int jb = (jg < G ? jg : 0) * RPG;
+    const float* wp = a.Wo + (int64_t)(h * 64 + jb) * d + cf * 4;
+    float4 w[RG::NWO_X];
+#pragma unroll
+    for (int i = 0; i < RG::NWO_X; i++) w[i] = ld_w4(wp + (int64_t)i * d);
+#pragma unroll
+    for (int i = 0; i < RG::NWO_X; i++) res_st(res, RG::WO_X + i, tid, w[i]);
+  }
 }
 
 

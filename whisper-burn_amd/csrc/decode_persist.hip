@@ -53,9 +53,11 @@ constexpr int PS_NGO = 16;      // wake-up words of the logits roles (a few hund
 // A few hundred logits blocks each folding the 4 d / 64 planes themselves pulled 22 MB through the fabric per step (write-
 // through data is not shared through the L2s); one block per row folds and normalises, and the logits blocks read d values.
 template <int DPL>
-__device__ __forceinline__ bool ps_finln_role(const PersistArgs& a, const int r, const PsStep& ps) {
+struct FinLnLds { alignas(16) float hs[64 * DPL]; };
+template <int DPL>
+__device__ __forceinline__ bool ps_finln_role(const PersistArgs& a, const int r, const PsStep& ps, FinLnLds<DPL>& sm) {
   constexpr int d = 64 * DPL, FP = 4 * DPL;
-  __shared__ __attribute__((aligned(16))) float hs[d];
+  auto& hs = sm.hs;
   const int tid = role_tid<true>(), lane = tid & 63, wave = tid >> 6;
   const int c = tid < d ? tid : 0;
   const float g_own = a.ln_g[c], b_own = a.ln_b[c];   // thread = column: every wave normalises its own 64 columns
@@ -105,17 +107,21 @@ __device__ __forceinline__ bool ps_finln_role(const PersistArgs& a, const int r,
 // rows arrive as granules from the final-LN roles.  Per row and tile the block leaves the best masked logit and its id --
 // greedy needs the argmax only (log_softmax is monotone: transcribe.rs:276 with beam.rs k = 1).
 template <int MR, int DPL>
+struct LogitsLds {
+  alignas(16) float xs[MR][64 * DPL];
+  alignas(16) float red[8][MR][PS_CT];
+  float tilev[MR][PS_CT];
+};
+template <int MR, int DPL>
 __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int tile0, const int n_t, const PsStep& ps,
-                                               const bool forced) {
+                                               const bool forced, LogitsLds<MR, DPL>& sm) {
   constexpr int d = 64 * DPL, NT = PS_NT, CT = PS_CT;
   constexpr int NR = d / 16;                        // E^T rows per thread: k = (2 wave + hh) NR + i
   constexpr int EPT = (MR * d + NT - 1) / NT;
   constexpr int PCH = EPT <= 3 ? 8 : EPT <= 6 ? 4 : 2;
   constexpr int NQ = MR * CT / NT;                  // tile values per thread in the column-sum pass
   constexpr bool TWO = DPL <= 6;                    // two tiles resident (2 x d / 16 float4 per thread) where they fit
-  __shared__ __attribute__((aligned(16))) float xs[MR][d];
-  __shared__ __attribute__((aligned(16))) float red[8][MR][CT];
-  __shared__ float tilev[MR][CT];
+  auto& xs = sm.xs; auto& red = sm.red; auto& tilev = sm.tilev;
   const int tid = role_tid<true>(), lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, c4 = (lane & 31) * 4;
   // (buffer loads: one lane offset, the row offset i vocab_ld rides in the scalar offset -- 24 64-bit addresses per lane
@@ -267,15 +273,15 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
 
 // ---- merge role: row r's argmax over the tiles, the chain's bookkeeping, the next step's embedding -------------------
 // (what dec_topk_merge_kernel + chained_update do between two launches; transcribe.rs:235-241 for the end of a row)
+struct MergeLds { float redv[8]; int redi[8]; unsigned tgt[8]; };
 __device__ __forceinline__ bool ps_merge_role(const PersistArgs& a, const int r, const int e, const PsStep& ps0,
-                                              const unsigned* clog, const int* n_per_ctr) {
-  __shared__ float redv[8];
-  __shared__ int redi[8];
+                                              const unsigned* clog, const int* n_per_ctr, MergeLds& sm) {
+  auto& redv = sm.redv; auto& redi = sm.redi;
   const int tid = role_tid<true>(), lane = tid & 63, wave = tid >> 6;
   const PsStep& ps = ps0;
   {
     // every logits role of this step has arrived (8 sharded counters, polled by 8 lanes at once)
-    __shared__ unsigned tgt[8];
+    auto& tgt = sm.tgt;
     if (tid < 8) tgt[tid] = (unsigned)(e + 1) * (unsigned)n_per_ctr[tid];
     __syncthreads();
     if (!hx_wait_many(clog, tgt, 8, ps.ctl, ps.step, 1000, ps.lds_flag)) return false;
@@ -341,9 +347,46 @@ __device__ __forceinline__ bool ps_merge_role(const PersistArgs& a, const int r,
 }
 
 // ---- the grid ---------------------------------------------------------------------------------------------------------
+// One LDS arena per block: the roles' arrays share one union (a block runs its roles one after another), the wait's
+// broadcast word follows, and what is left of the CU's 160 KB holds the resident operands of a block whose role list has
+// exactly one layer role, a self- or cross-attention one (decode_fused_bodies.h: ResGeom) -- whole per-thread float4 slots.
+template <int DPL, int MR, int NP>
+union PsRoleLds {
+  MlpLds<MR, DPL, false> mlp; AttnLds<DPL> attn; CrossLds<DPL, NP> cross;
+  FinLnLds<DPL> finln; LogitsLds<MR, DPL> logits; MergeLds merge;
+};
+constexpr int PS_LDS_BYTES = 160 * 1024;
+// (d >= 384 with 8 rows or with the two-pass key ring keeps the streamed path: those instances sit hardest at the register
+// limit, and with the resident path compiled in each spilled one dword more than before)
+constexpr bool ps_resident_instance(int DPL, int MR, int NP) { return !(DPL >= 6 && (MR == 8 || NP == 2)); }
+template <int DPL, int MR, int NP>
+struct PsArena {
+  static constexpr int ROLE_BYTES = (int)((sizeof(PsRoleLds<DPL, MR, NP>) + 15) / 16 * 16);
+  static constexpr int FLAG_BYTES = 16;             // wait_flag, padded: the resident region stays 16-byte aligned
+  static constexpr int RS = ps_resident_instance(DPL, MR, NP) ? (PS_LDS_BYTES - ROLE_BYTES - FLAG_BYTES) / (PS_NT * 16) : 0;   // resident float4 slots per thread
+  static constexpr int BYTES = ROLE_BYTES + FLAG_BYTES + RS * PS_NT * 16;   // each of the three objects padded to 16 bytes
+  static_assert(RS >= 0 && BYTES <= PS_LDS_BYTES, "the persistent kernel's LDS arena exceeds 160 KB");
+  // (does anything useful fit?)
+  static constexpr bool USEFUL = ResGeom<DPL, NP, RS>::WO_A + ResGeom<DPL, NP, RS>::NWO_A + ResGeom<DPL, NP, RS>::WO_X +
+                                 ResGeom<DPL, NP, RS>::NWO_X > 0;
+};
+static_assert(PS_NT == ROLE_NT, "block size");
+#define WB_PS_INSTANCES(X) X(2, 4, 1) X(2, 8, 1) X(6, 4, 1) X(6, 8, 1) X(8, 4, 1) X(2, 4, 2) X(6, 4, 2) X(8, 4, 2)
+#define WB_PS_CHECK(DPL_, MR_, NP_) static_assert(PsArena<DPL_, MR_, NP_>::BYTES <= 160 * 1024, "LDS arena of an instance");
+WB_PS_INSTANCES(WB_PS_CHECK)
+#undef WB_PS_CHECK
+
 template <int DPL, int MR, int NP>
 __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
-  __shared__ int wait_flag;
+  using AR = PsArena<DPL, MR, NP>;
+  constexpr int RS = AR::RS;
+  // (three objects, not one struct: as members of one struct the bench instance spilled 36 B per lane instead of 20.  The
+  // compiler may pack them a few bytes tighter than AR::BYTES, which pads each to 16: the asserted number is an upper bound)
+  __shared__ PsRoleLds<DPL, MR, NP> lds;
+  __shared__ __attribute__((aligned(16))) int wait_flag[AR::FLAG_BYTES / 4];
+  __shared__ __attribute__((aligned(16))) float4 res_buf[RS > 0 ? RS * PS_NT : 1];
+  static_assert(sizeof(lds) <= AR::ROLE_BYTES && sizeof(wait_flag) == AR::FLAG_BYTES && sizeof(res_buf) <= (RS > 0 ? RS : 1) * PS_NT * 16 &&
+                AR::BYTES + (RS > 0 ? 0 : 16) <= PS_LDS_BYTES, "the three LDS objects are what PsArena accounts for");
   const int NL = a.n_layer, S = a.S, R = a.n_rows, H = a.n_head, NB = a.nb_mlp;
   // arrival counter c lives at ctl[HX_HDR + c HX_LINE]: one 128-byte line each
   auto cptr = [&](int c) { return reinterpret_cast<unsigned*>(a.ctl + HX_HDR + c * HX_LINE); };
@@ -352,13 +395,27 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
 #pragma unroll
   for (int k = 0; k < 8; k++) n_per_ctr[k] = (a.n_logits_roles + 7 - k) / 8;
   const int i_lo = a.role_off[blockIdx.x], i_hi = a.role_off[blockIdx.x + 1];
+  // resident operands: the host names the role of a block whose ONE layer role is a self- or cross-attention role
+  // (res_role); loaded once, here -- the weights are constant and the window's cached cross V is constant for the launch
+#if defined(WB_PS_DRY)                              // (dry build: no operand loads at all)
+  constexpr bool RES = false;
+#else
+  constexpr bool RES = RS > 0;
+#endif
+  int res_i = -1;
+  if (RES && a.res_role != nullptr) res_i = a.res_role[blockIdx.x];
+  if (res_i >= i_lo && res_i < i_hi) {
+    const PsRole role = a.roles[res_i];
+    if (role.kind == PSR_ATTN) dec_attn_res_fill<DPL, RS>(a.layers[role.layer].attn, role.a, res_buf);
+    else if (role.kind == PSR_CROSS) dec_cross_res_fill<DPL, NP, RS>(a.layers[role.layer].cross, role.a, role.b, res_buf);
+  }
   unsigned long long dead_seen = 0;                 // bit k: role i_lo + k of this block has found its row dead (it stays dead)
   for (int e = 0; e < a.n_steps; e++) {
     for (int i = i_lo; i < i_hi; i++) {
       const PsRole role = a.roles[i];
       PsStep ps;
       ps.known_dead = i - i_lo < 64 && ((dead_seen >> (i - i_lo)) & 1ull) != 0;
-      ps.ctl = a.ctl; ps.step = a.step0 + e; ps.n_rows = R; ps.dead = a.dead; ps.lds_flag = &wait_flag;
+      ps.ctl = a.ctl; ps.step = a.step0 + e; ps.n_rows = R; ps.dead = a.dead; ps.lds_flag = &wait_flag[0];
       unsigned long long* stp = a.stamps ? a.stamps + ((size_t)e * a.n_roles + i) * PS_STAMPS : nullptr;
       if (stp && threadIdx.x == 0) stp[0] = wall_clock64();
       ps.stamp = stp;
@@ -374,7 +431,7 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         else { ps.ctr_index = C_CROSS + role.layer - 1; ps.target = (unsigned)(e + 1) * H * R; }
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_out = tag_l; ps.tag_in = tag_l - 1u;
-        ok = dec_attn_body<DPL, true>(la, role.a, role.b, ps);
+        ok = dec_attn_body<DPL, true, RS>(la, role.a, role.b, ps, lds.attn, i == res_i ? res_buf : nullptr);
         out = C_ATTN + role.layer * S + role.b;
       } else if (role.kind == PSR_CROSS) {
         const CrossFusedArgs la = a.layers[role.layer].cross;
@@ -383,7 +440,7 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         else { ps.ctr_index = C_MLP + role.layer - 1; ps.target = (unsigned)(e + 1) * NB; }
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_out = tag_l + 1u; ps.tag_in = tag_l;
-        ok = dec_cross_body<DPL, true, NP>(la, role.a, role.b, ps);
+        ok = dec_cross_body<DPL, true, NP, RS>(la, role.a, role.b, ps, lds.cross, i == res_i ? res_buf : nullptr);
         out = C_CROSS + role.layer;
       } else if (role.kind == PSR_MLP) {
         const MlpFusedArgs la = a.layers[role.layer].mlp;
@@ -391,13 +448,13 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         ps.ctr_index = C_ATTN + role.layer * S; ps.target = (unsigned)(e + 1) * H; ps.n_ctr = R;
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_out = tag_l + 2u; ps.tag_in = tag_l + 1u;
-        ok = dec_mlp_body<MR, DPL, false, true>(la, role.a, ps);
+        ok = dec_mlp_body<MR, DPL, false, true>(la, role.a, ps, lds.mlp);
         out = C_MLP + role.layer;
       } else if (role.kind == PSR_FINLN) {
         ps.ctr_index = C_CROSS + NL - 1; ps.target = (unsigned)(e + 1) * H * R;
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_in = tag_l + 2u; ps.tag_out = tag_l + 2u;
-        ok = ps_finln_role<DPL>(a, role.b, ps);
+        ok = ps_finln_role<DPL>(a, role.b, ps, lds.finln);
         out = C_GO + PS_NGO;                         // (nobody waits for it: the logits roles watch the granules)
       } else if (role.kind == PSR_LOGITS) {
         // a few hundred blocks: pre-woken by the last cross-attention block of the step through one of PS_NGO words; they
@@ -406,10 +463,10 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         ps.ctr_index = C_GO + (role.layer % PS_NGO); ps.target = (unsigned)(e + 1);
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_in = tag_l + 2u;
-        ok = ps_logits_role<MR, DPL>(a, role.a, role.b, ps, e < a.n_forced);
+        ok = ps_logits_role<MR, DPL>(a, role.a, role.b, ps, e < a.n_forced, lds.logits);
         out = C_LOG + (role.layer & 7);
       } else {
-        ok = ps_merge_role(a, role.b, e, ps, cptr(C_LOG), n_per_ctr);
+        ok = ps_merge_role(a, role.b, e, ps, cptr(C_LOG), n_per_ctr, lds.merge);
         out = C_X + role.b;
       }
       if (!ok) return;                               // the decode was stopped (or a wait gave up): leave
@@ -439,10 +496,22 @@ int max_blocks_per_cu() {
 
 }  // namespace
 
+// resident float4 slots per thread of the instance that serves (d, n_rows, max_keys); 0: none, or nothing useful fits
+int dec_persist_resident_slots(int d, int n_rows, int max_keys) {
+  if (!dec_persist_supported(d, n_rows, max_keys)) return 0;
+  const int dpl = d / 64, mr = n_rows > 4 ? 8 : 4, np = max_keys > CROSS_FUSED_MAX_C ? 2 : 1;
+#define WB_PS_SLOTS(DPL_, MR_, NP_) \
+  if (dpl == DPL_ && mr == MR_ && np == NP_) return PsArena<DPL_, MR_, NP_>::USEFUL ? PsArena<DPL_, MR_, NP_>::RS : 0;
+  WB_PS_INSTANCES(WB_PS_SLOTS)
+#undef WB_PS_SLOTS
+  return 0;
+}
+
 int ps_ctl_ints(int S, int n_layer) { return HX_HDR + (S + n_layer * S + 2 * n_layer + 8 + PS_NGO + 1) * HX_LINE; }
 
-// d = 512 with more than 4 rows would need > 160 KB of LDS (every role's LDS is resident at once); so would the two-pass
-// cross-attention role (768 < C <= 1536 keys: the opt-in 30 s window) next to the 8-row MLP role
+// The shapes the kernel is instantiated for: d = 128 / 384 with up to 8 rows, d = 512 with up to 4, two key passes (768 < C <=
+// 1536 keys: the opt-in 30 s window) with up to 4 rows.  (The limits date from the time every role's LDS was allocated side by
+// side; with the roles in one union LDS no longer sets them, but the other shapes are not instantiated or tested.)
 bool dec_persist_supported(int d, int n_rows, int max_keys) {
   if (n_rows < 1 || n_rows > 8) return false;
   if (max_keys > CROSS_FUSED_MAX_PASSES * CROSS_FUSED_MAX_C) return false;
