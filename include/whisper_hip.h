@@ -417,6 +417,57 @@ int wb_stitch_windows_times(const int32_t* win_tokens, int32_t row_stride, const
                             int max_n_offsets, int min_n_overlaps, int32_t* out, int64_t cap, int64_t* n_out,
                             const float* win_times, float* out_times);
 
+/* ---- token log-probabilities, no-speech probability, language detection ------------------------------------------
+ * One teacher-forced pass of the decoder over finished token rows, ended by a fused logits product (score.hip) that keeps
+ * only log-softmax statistics: exact f32 MFMA, no [rows][V] logits in memory, run-to-run bit-identical.
+ *
+ * token_logprobs [n][L]: for 1 <= l < len, entry l = log_softmax(logits at position l - 1)[tokens[l]]; the special mask
+ *        (is_special, as wb_session_set_special_mask) is added first when l <= mask_until_len (transcribe.rs:271-275: a
+ *        sequence of length l predicts index l; 0 = never).  Entry 0 and entries >= len are NaN.
+ * probe_logprobs [n][n_probe] (optional, NULL / 0): the UNMASKED log_softmax at position probe_pos of the ids probe_ids
+ *        (the no-speech token after [SOT], the language ids).  probe_pos may be a masked position: both statistics of such
+ *        a row are kept.
+ * A NaN in the decoder's output row gives NaN for that position (never a finite-looking number); a position whose whole
+ * vocabulary is masked (no real special mask does that) has lse = -inf and a NaN log-prob.
+ * lens:  per-row length, NULL = L.
+ * Errors (nothing is launched): a token / probe id outside the vocabulary, len outside 1 .. L, probe_pos >= len of any
+ * row, mask_until_len > 0 without is_special -> WB_ERR_ARG; len > n_text_ctx -> WB_ERR_SHAPE. */
+int wb_score_tokens(wb_model* m, const int32_t* tokens, int n, int L, const int32_t* lens, const float* enc, int C,
+                    const uint8_t* is_special, int32_t mask_until_len, const int32_t* probe_ids, int32_t n_probe,
+                    int32_t probe_pos, float* token_logprobs, float* probe_logprobs);
+/* The same over a session's windows, after (or without) a decode: row w belongs to window w and uses the session's cached
+ * cross-attention K/V -- no re-encode.  The mask is the one set by wb_session_set_special_mask: WB_ERR_STATE when
+ * mask_until_len > 0 and none was set.  token_logprobs [W][row_stride]. */
+int wb_session_score(wb_session* s, const int32_t* tokens, int32_t row_stride, const int32_t* lens,
+                     int32_t mask_until_len, const int32_t* probe_ids, int32_t n_probe, int32_t probe_pos,
+                     float* token_logprobs, float* probe_logprobs);
+/* Whisper's detect_language: encode the first max_windows windows of the waveform (0 = all; the windows of
+ * wb_waveform_to_tokens with its default overlap), score the one-token rows [tok_start_of_transcript] with lang_ids as
+ * probes, and restrict the softmax to lang_ids (on the host, in f64): win_probs [W][n_lang] (optional), mean_probs [n_lang]
+ * (optional) = the mean over the W windows, *best = its argmax as an index into lang_ids (lowest on a tie). */
+int wb_waveform_detect_language(wb_model* m, const float* pcm, int64_t n, int sample_rate, int32_t padding,
+                                int32_t tok_start_of_transcript, const int32_t* lang_ids, int32_t n_lang,
+                                int32_t max_windows, float* win_probs, float* mean_probs, int32_t* best);
+/* wb_waveform_to_tokens + the scores of every window's row as decoded, on the session that decoded it (mask_until_len from
+ * p).  win_logprobs [n_local][row_stride] as token_logprobs above; stitched_logprobs parallel to `stitched` (required with
+ * it); win_avg_logprob [n_local] = mean of entries [4, len) -- Whisper's avg_logprob: the generated tokens, a final
+ * end-of-text included; NaN when empty; win_no_speech_prob [n_local] = exp of the unmasked log-prob of tok_no_speech after
+ * [SOT] (NaN when tok_no_speech < 0). */
+int wb_waveform_to_token_scores(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                                const uint8_t* is_special, int win_begin, int win_end, int32_t* win_tokens,
+                                int32_t row_stride, int32_t* win_lens, int32_t* stitched, int64_t stitched_cap,
+                                int64_t* n_stitched, int32_t tok_no_speech, float* win_logprobs,
+                                float* stitched_logprobs, float* win_avg_logprob, float* win_no_speech_prob);
+/* Test hook: the two launches of score.hip alone on caller data (host memory).  h [R][d] (d % 32 == 0), E [V][d]; E^T is
+ * built inside with leading dimension V rounded up to 64 and NaN in the pad columns.  mask [V] (0 / -inf) applies to the
+ * rows with row_masked[r] != 0 (both NULL: no mask); target[r] in [0, V) or -1; probes (probe_row[p], probe_id[p]) are
+ * scored unmasked; v_splits 0 = auto.  logprob [R] (NaN without a target), lse [R] (under the row's mask), probe_lp
+ * [n_probe].  `device` only hosts the buffers (no model). */
+int wb_logprob_gather(int device, const float* h, int32_t R, int32_t d, const float* E, int32_t V, const float* mask,
+                      const uint8_t* row_masked, const int32_t* target, const int32_t* probe_row,
+                      const int32_t* probe_id, int32_t n_probe, int32_t v_splits, float* logprob, float* lse,
+                      float* probe_lp);
+
 /* The reference's retired greedy decoder kept its repetition detectors (transcribe.rs:385-447, dead code there):
  *   wb_first_repetition_end        :385-393   (period > n, a usize underflow panic there -> WB_ERR_ARG)
  *   wb_repetition_period           :395-417   returns the period, 0 for None

@@ -107,6 +107,27 @@ extern "C" {
     pub fn wb_stitch_windows_times(win_tokens: *const i32, row_stride: i32, win_lens: *const i32, n_windows: c_int,
                                    max_n_offsets: c_int, min_n_overlaps: c_int, out: *mut i32, cap: i64, n_out: *mut i64,
                                    win_times: *const c_float, out_times: *mut c_float) -> c_int;
+    // token log-probabilities, no-speech probability, language detection: a teacher-forced pass ended by a fused
+    // log-softmax product that never forms the logits (no counterpart in the reference)
+    pub fn wb_score_tokens(m: *mut wb_model, tokens: *const i32, n: c_int, L: c_int, lens: *const i32, enc: *const c_float,
+                           C: c_int, is_special: *const u8, mask_until_len: i32, probe_ids: *const i32, n_probe: i32,
+                           probe_pos: i32, token_logprobs: *mut c_float, probe_logprobs: *mut c_float) -> c_int;
+    pub fn wb_session_score(s: *mut wb_session, tokens: *const i32, row_stride: i32, lens: *const i32, mask_until_len: i32,
+                            probe_ids: *const i32, n_probe: i32, probe_pos: i32, token_logprobs: *mut c_float,
+                            probe_logprobs: *mut c_float) -> c_int;
+    pub fn wb_waveform_detect_language(m: *mut wb_model, pcm: *const c_float, n: i64, sample_rate: c_int, padding: i32,
+                                       tok_start_of_transcript: i32, lang_ids: *const i32, n_lang: i32, max_windows: i32,
+                                       win_probs: *mut c_float, mean_probs: *mut c_float, best: *mut i32) -> c_int;
+    pub fn wb_waveform_to_token_scores(m: *mut wb_model, pcm: *const c_float, n: i64, sample_rate: c_int,
+                                       p: *const wb_decode_params, is_special: *const u8, win_begin: c_int, win_end: c_int,
+                                       win_tokens: *mut i32, row_stride: i32, win_lens: *mut i32, stitched: *mut i32,
+                                       stitched_cap: i64, n_stitched: *mut i64, tok_no_speech: i32,
+                                       win_logprobs: *mut c_float, stitched_logprobs: *mut c_float,
+                                       win_avg_logprob: *mut c_float, win_no_speech_prob: *mut c_float) -> c_int;
+    pub fn wb_logprob_gather(device: c_int, h: *const c_float, R: i32, d: i32, E: *const c_float, V: i32,
+                             mask: *const c_float, row_masked: *const u8, target: *const i32, probe_row: *const i32,
+                             probe_id: *const i32, n_probe: i32, v_splits: i32, logprob: *mut c_float, lse: *mut c_float,
+                             probe_lp: *mut c_float) -> c_int;
     pub fn wb_session_begin(m: *mut wb_model, pcm: *const c_float, n_pcm: i64, starts: *const i64, lens: *const i64,
                             n_windows: c_int, max_beams: c_int, padding: c_int, out: *mut *mut wb_session) -> c_int;
     pub fn wb_session_set_special_mask(s: *mut wb_session, is_special: *const u8) -> c_int;

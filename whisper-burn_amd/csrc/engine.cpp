@@ -394,6 +394,44 @@ int run_encoder_unguarded(wb_model* m, hipStream_t st, Workspace& ws, const MelB
   return WB_OK;
 }
 
+// Every ResidualDecoderAttentionBlock (mod.rs:345-350) of a teacher-forced pass over `rows` packed token rows, in place on
+// the workspace's residual stream ws.x (scratch: ws.h / qkv / att / hm, sized by the caller).  sg: n masked self-attention
+// segments followed by n cross-attention segments; the pre-scaled cross K|V of layer i at ckv + i * layer_stride, rows of
+// ldkv.  Shared by the stateless decoder and the scoring pass: one wiring of the column scales and the residual adds.
+static int decoder_blocks(wb_model* m, hipStream_t st, Workspace& ws, int rows, int n, int L, const AttnSeg* sg,
+                          const float* ckv, int64_t layer_stride, int ldkv) {
+  const int d = m->dims.n_text_state, H = m->dims.n_text_head, NL = m->dims.n_text_layer;
+  float *x = ws.x.as<float>(), *h = ws.h.as<float>(), *qkv = ws.qkv.as<float>(), *att = ws.att.as<float>(),
+        *hm = ws.hm.as<float>();
+  GemmArgs g;
+  for (int i = 0; i < NL; i++) {   // ResidualDecoderAttentionBlock::forward, mod.rs:345-350
+    const DecBlockW& b = m->dec[i];
+    launch_layernorm(st, x, h, rows, d, b.ln1.g, b.ln1.b, b.ln1.eps, m->ln_eps_inside_sqrt);
+    g = linear_args(h, rows, b.qkv, qkv);
+    g.col_scale = m->qk_scale; g.col_scale_period = 3 * d; g.col_scale_width = 2 * d;
+    WB_TRY(gemm(m, st, g, &b.qkv));
+    launch_attention_f32(st, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, sg, n, L, H, 1.0f, 1);
+    g = linear_args(att, rows, b.out, x);
+    g.residual = x; g.ldr = d;
+    WB_TRY(gemm(m, st, g, &b.out));
+    launch_layernorm(st, x, h, rows, d, b.ln2.g, b.ln2.b, b.ln2.eps, m->ln_eps_inside_sqrt);
+    g = linear_args(h, rows, b.cq, qkv);
+    g.col_scale = m->qk_scale; g.col_scale_period = d; g.col_scale_width = d;
+    WB_TRY(gemm(m, st, g, &b.cq));
+    const float* Kl = ckv + (size_t)i * layer_stride;
+    launch_attention_f32(st, qkv, d, Kl, Kl + d, ldkv, att, d, sg + n, n, L, H, 1.0f, 0);
+    g = linear_args(att, rows, b.cout, x);
+    g.residual = x; g.ldr = d;
+    WB_TRY(gemm(m, st, g, &b.cout));
+    launch_layernorm(st, x, h, rows, d, b.ln3.g, b.ln3.b, b.ln3.eps, m->ln_eps_inside_sqrt);
+    g = linear_args(h, rows, b.mlp1, hm);
+    g.act = ACT_GELU;
+    WB_TRY(gemm(m, st, g, &b.mlp1));
+    WB_TRY(gemm_residual_kblocked(m, st, hm, rows, b.mlp2, x));
+  }
+  return WB_OK;
+}
+
 static int run_decoder_stateless_body(wb_model* m, hipStream_t st, Workspace& ws, const int32_t* tokens_dev, int n, int L,
                                       const float* enc_dev, int C, float* logits_dev);
 int run_decoder_stateless(wb_model* m, hipStream_t st, Workspace& ws, const int32_t* tokens_dev, int n, int L,
@@ -431,31 +469,7 @@ static int run_decoder_stateless_body(wb_model* m, hipStream_t st, Workspace& ws
   GemmArgs g = linear_args(enc_dev, krows, m->ckv_all, ckv);
   g.col_scale = m->qk_scale; g.col_scale_period = 2 * d; g.col_scale_width = d;
   WB_TRY(gemm(m, st, g, &m->ckv_all));
-  for (int i = 0; i < NL; i++) {   // ResidualDecoderAttentionBlock::forward, mod.rs:345-350
-    const DecBlockW& b = m->dec[i];
-    launch_layernorm(st, x, h, rows, d, b.ln1.g, b.ln1.b, b.ln1.eps, m->ln_eps_inside_sqrt);
-    g = linear_args(h, rows, b.qkv, qkv);
-    g.col_scale = m->qk_scale; g.col_scale_period = 3 * d; g.col_scale_width = 2 * d;
-    WB_TRY(gemm(m, st, g, &b.qkv));
-    launch_attention_f32(st, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, sg, n, L, H, 1.0f, 1);
-    g = linear_args(att, rows, b.out, x);
-    g.residual = x; g.ldr = d;
-    WB_TRY(gemm(m, st, g, &b.out));
-    launch_layernorm(st, x, h, rows, d, b.ln2.g, b.ln2.b, b.ln2.eps, m->ln_eps_inside_sqrt);
-    g = linear_args(h, rows, b.cq, qkv);
-    g.col_scale = m->qk_scale; g.col_scale_period = d; g.col_scale_width = d;
-    WB_TRY(gemm(m, st, g, &b.cq));
-    launch_attention_f32(st, qkv, d, ckv + (size_t)i * 2 * d, ckv + (size_t)i * 2 * d + d, ldkv, att, d, sg + n, n,
-                         L, H, 1.0f, 0);
-    g = linear_args(att, rows, b.cout, x);
-    g.residual = x; g.ldr = d;
-    WB_TRY(gemm(m, st, g, &b.cout));
-    launch_layernorm(st, x, h, rows, d, b.ln3.g, b.ln3.b, b.ln3.eps, m->ln_eps_inside_sqrt);
-    g = linear_args(h, rows, b.mlp1, hm);
-    g.act = ACT_GELU;
-    WB_TRY(gemm(m, st, g, &b.mlp1));
-    WB_TRY(gemm_residual_kblocked(m, st, hm, rows, b.mlp2, x));
-  }
+  WB_TRY(decoder_blocks(m, st, ws, rows, n, L, sg, ckv, 2 * d, ldkv));
   launch_layernorm(st, x, h, rows, d, m->ln_dec.g, m->ln_dec.b, m->ln_dec.eps, m->ln_eps_inside_sqrt);
   // logits = x . token_embedding^T (mod.rs:156), streamed from the [d][Vp] transposed copy
   GemmArgs lg;
@@ -572,6 +586,85 @@ int run_align(wb_model* m, hipStream_t st, Workspace& ws, AlignJob& J) {
                WB_ERR_SHAPE, "align: DTW of %d rows unsupported", maxN);
   }
   WB_HIP(hipGetLastError());
+  return WB_OK;
+}
+
+// The scoring pass: run_decoder_stateless_body's layers over ragged rows, then score.hip instead of the [R][V] logits GEMM.
+int run_score(wb_model* m, hipStream_t st, Workspace& ws, ScoreJob& J) {
+  const wb_dims& D = m->dims;
+  const int d = D.n_text_state, H = D.n_text_head, NL = D.n_text_layer, V = D.n_vocab;
+  const int n = J.n, L = J.L, rows = n * L, NP = (int)J.probe_ids.size();
+  WB_REQUIRE(n > 0 && L > 0 && d == 64 * H, WB_ERR_SHAPE, "score: unsupported shape");
+  ScoreBufs& B = ws.score;
+  J.segs_host.resize(2 * n);
+  // one staging array, one upload: tokens [rows] | target [rows] | probe_row [n NP] | probe_id [n NP] | row_masked [rows] bytes
+  const size_t o_tgt = (size_t)rows, o_prow = 2 * (size_t)rows, o_pid = o_prow + (size_t)n * NP, o_msk = o_pid + (size_t)n * NP;
+  J.i32_host.assign(o_msk + ((size_t)rows + 3) / 4, 0);
+  std::copy(J.tokens.begin(), J.tokens.end(), J.i32_host.begin());
+  std::fill(J.i32_host.begin() + o_tgt, J.i32_host.begin() + o_prow, -1);
+  uint8_t* msk_host = reinterpret_cast<uint8_t*>(J.i32_host.data() + o_msk);
+  for (int i = 0; i < n; i++) {
+    J.segs_host[i] = AttnSeg{i * L, J.len[i], i * L, J.len[i]};              // masked self-attention
+    J.segs_host[n + i] = AttnSeg{i * L, J.len[i], J.kv_row0[i], J.C[i]};     // cross-attention
+    for (int l = 0; l + 1 < J.len[i]; l++) {
+      J.i32_host[o_tgt + (size_t)i * L + l] = J.tokens[(size_t)i * L + l + 1];
+      // transcribe.rs:271-275: a sequence of length l + 1 predicts index l + 1 under the mask while l + 1 <= mask_until_len
+      msk_host[(size_t)i * L + l] = J.mask_until_len > 0 && l + 1 <= J.mask_until_len;
+    }
+    for (int p = 0; p < NP; p++) {
+      J.i32_host[o_prow + (size_t)i * NP + p] = i * L + J.probe_pos;
+      J.i32_host[o_pid + (size_t)i * NP + p] = J.probe_ids[p];
+    }
+  }
+  const int vs = score_splits(rows, V, J.v_splits);
+  WB_TRY(upload(st, ws.segs, J.segs_host.data(), J.segs_host.size() * sizeof(AttnSeg)));
+  ws.enc_T.clear();                   // (ws.segs no longer holds the encoder's segments)
+  WB_TRY(upload(st, B.i32, J.i32_host.data(), J.i32_host.size() * 4));
+  WB_TRY(B.part.ensure((size_t)vs * rows * sizeof(float4)));
+  // f32 results: target_logit [rows] | lse [rows] | probe_logit [n NP] | logprob [rows] | probe_lp [n NP] (the last two: one copy)
+  WB_TRY(B.f32.ensure(((size_t)3 * rows + 2 * (size_t)n * NP) * 4));
+  WB_TRY(ws.x.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.h.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.qkv.ensure((size_t)rows * 3 * d * 4));
+  WB_TRY(ws.att.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.hm.ensure((size_t)rows * 4 * d * 4));
+  float *x = ws.x.as<float>(), *h = ws.h.as<float>(), *qkv = ws.qkv.as<float>(), *att = ws.att.as<float>(),
+        *hm = ws.hm.as<float>();
+  const AttnSeg* sg = ws.segs.as<AttnSeg>();
+  const float* ckv = J.ckv;
+  int64_t layer_stride = J.ckv_layer_stride;
+  int ldkv = J.ldkv;
+  GemmArgs g;
+  if (J.enc_dev) {   // cross K|V of every layer in one GEMM, K pre-scaled (as run_decoder_stateless_body)
+    ldkv = NL * 2 * d; layer_stride = 2 * d;
+    WB_TRY(ws.x1.ensure((size_t)J.enc_rows * ldkv * 4));
+    g = linear_args(J.enc_dev, J.enc_rows, m->ckv_all, ws.x1.as<float>());
+    g.col_scale = m->qk_scale; g.col_scale_period = 2 * d; g.col_scale_width = d;
+    WB_TRY(gemm(m, st, g, &m->ckv_all));
+    ckv = ws.x1.as<float>();
+  }
+  // (rows past a row's len: as in run_align -- every operator is row-independent, nothing reads their results)
+  launch_embed(st, B.i32.as<int32_t>(), rows, L, d, m->tok_emb, m->dec_pos, x);
+  WB_TRY(decoder_blocks(m, st, ws, rows, n, L, sg, ckv, layer_stride, ldkv));
+  launch_layernorm(st, x, h, rows, d, m->ln_dec.g, m->ln_dec.b, m->ln_dec.eps, m->ln_eps_inside_sqrt);
+  ScoreArgs a;
+  a.h = h; a.R = rows; a.d = d; a.Et = m->tok_emb_t; a.ldv = m->vocab_ld; a.V = V;
+  a.mask = J.mask_until_len > 0 ? J.mask_dev : nullptr;
+  a.row_masked = reinterpret_cast<const uint8_t*>(B.i32.as<int32_t>() + o_msk);
+  a.target = B.i32.as<int32_t>() + o_tgt;
+  a.probe_row = B.i32.as<int32_t>() + o_prow; a.probe_id = B.i32.as<int32_t>() + o_pid; a.n_probe = n * NP;
+  a.vs = vs;
+  a.part = B.part.as<float4>();
+  a.target_logit = B.f32.as<float>(); a.lse = a.target_logit + rows; a.probe_logit = a.lse + rows;
+  a.logprob = a.probe_logit + (size_t)n * NP; a.probe_lp = a.logprob + rows;
+  // algorithmic bytes: E^T once per row tile that streams it, h once per split
+  prof_tag(KC_SCORE_LOGITS, (double)m->vocab_ld * d * 4 * ((rows + SCORE_BM - 1) / SCORE_BM) + (double)rows * d * 4 * vs);
+  WB_REQUIRE(launch_score_logits(st, a) == 0, WB_ERR_SHAPE, "score: unsupported shape (rows %d, d %d, V %d)", rows, d, V);
+  prof_tag(KC_SCORE_MERGE, (double)vs * rows * sizeof(float4));
+  launch_score_merge(st, a);
+  WB_HIP(hipGetLastError());
+  J.result_host.resize((size_t)rows + (size_t)n * NP);       // logprob [rows] | probe_lp [n NP]
+  WB_HIP(hipMemcpyAsync(J.result_host.data(), a.logprob, J.result_host.size() * 4, hipMemcpyDeviceToHost, st));
   return WB_OK;
 }
 

@@ -58,6 +58,30 @@ struct AlignJob {
   std::vector<AttnSeg> segs_host; std::vector<DtwSeg> dtw_host;
 };
 int run_align(wb_model* m, hipStream_t st, Workspace& ws, AlignJob& job);
+
+// Token scoring (score.hip): one teacher-forced pass of the whole decoder over n token rows (ragged like AlignJob: rows
+// packed with stride L, positions past a row's len carry token 0 and their results are never read), ended by the fused
+// logits product that keeps only log-softmax statistics.  Row r = i * L + l is position l of token row i: its target is
+// tokens[i][l + 1] (none at the row's last position), scored under `mask_dev` when l + 1 <= mask_until_len; the probes sit
+// at position probe_pos of every row, always unmasked.  Everything is enqueued on `st`; the caller synchronises once and
+// then reads result_host: logprob [n * L], then probe_lp [n * n_probe].
+struct ScoreJob {
+  int n = 0, L = 0;
+  std::vector<int32_t> tokens;            // [n][L]
+  std::vector<int> len, C, kv_row0;       // per row: tokens, encoder positions, first row of its window in the K/V source
+  const float* enc_dev = nullptr;         // non-null: project the cross K|V here (enc_rows x d input); else use ckv
+  int enc_rows = 0;
+  const float* ckv = nullptr;             // cached pre-scaled cross K|V: layer i at ckv + i * ckv_layer_stride, rows of ldkv
+  int64_t ckv_layer_stride = 0; int ldkv = 0;
+  const float* mask_dev = nullptr;        // [V] 0 / -inf (needed when mask_until_len > 0)
+  int mask_until_len = 0;
+  std::vector<int32_t> probe_ids; int probe_pos = 0;
+  int v_splits = 0;                       // 0: auto
+  // host staging (outlives the enqueued copies) and results
+  std::vector<AttnSeg> segs_host; std::vector<int32_t> i32_host;
+  std::vector<float> result_host;
+};
+int run_score(wb_model* m, hipStream_t st, Workspace& ws, ScoreJob& job);
 extern std::mutex g_stateless_mu;       // api.cpp: serialises the stateless entry points (they share the model's scratch)
 
 // split-precision fp16 MFMA GEMM when split copies sh / sl ([N][ldwt] fp16) are given and the shape fits, else exact-f32 MFMA

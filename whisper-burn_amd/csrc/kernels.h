@@ -18,6 +18,8 @@ enum KernelClass {
   KC_B_LOGITS_GEMM, KC_B_TOPK_ROWS, KC_PERSIST, KC_BEAM_UPDATE, KC_FOLD_LN_ROWS,
   // token alignment (align.hip): at most two launches per decoder layer that owns an alignment head, one DTW launch
   KC_ALIGN_STATS, KC_ALIGN_ACCUM, KC_ALIGN_DTW,
+  // token scoring (score.hip): one launch each per scoring call
+  KC_SCORE_LOGITS, KC_SCORE_MERGE,
   KC_COUNT
 };
 void prof_tag(int cls, double algo_bytes);
@@ -172,5 +174,30 @@ int launch_align_accumulate(hipStream_t st, const float* Q, int ldq, const float
 struct DtwSeg { int32_t x_row0, n, c, out0; };
 int launch_align_dtw(hipStream_t st, const float* X, int ldx, int negate, const DtwSeg* segs_dev, int n_rows, int max_n,
                      uint32_t* trace, int64_t trace_stride, int ldt, int32_t* out);
+
+// ---- token scoring (score.hip): log-softmax statistics of h E^T without the logits --------------------------------------
+// h [R][d] (the final-LayerNorm rows, d % 32 == 0, 16-byte aligned) x Et [d][ldv] (E^T, ldv % 4 == 0, ldv >= V; columns
+// [V, ldv) are read and contribute nothing).  Grid: ceil(R / SCORE_BM) row tiles x vs vocabulary splits; split s owns the
+// SCORE_BN-column tiles [s T / vs, (s + 1) T / vs) of the T = ceil(V / SCORE_BN) tiles.
+// mask [V] (0 / -inf, may be null) is added to the rows with row_masked[r] != 0 only; target[r] in [0, V) or -1;
+// probes (probe_row[p] in [0, R), probe_id[p] in [0, V)) are always scored without the mask.
+constexpr int SCORE_BM = 32, SCORE_BN = 128;
+struct ScoreArgs {
+  const float* h = nullptr; int R = 0, d = 0;
+  const float* Et = nullptr; int ldv = 0, V = 0;
+  const float* mask = nullptr; const uint8_t* row_masked = nullptr;
+  const int32_t* target = nullptr;
+  const int32_t* probe_row = nullptr; const int32_t* probe_id = nullptr; int n_probe = 0;
+  int vs = 1;
+  // written by score_logits_kernel: part [vs][R] = (max, sum exp(x - max)) of the row's own statistic (masked when
+  // row_masked) and of the unmasked one; target_logit [R] (rows with a target; under the row's mask); probe_logit [n_probe]
+  float4* part = nullptr; float* target_logit = nullptr; float* probe_logit = nullptr;
+  // written by score_merge_kernel: lse [R] (own statistic), logprob [R] = target_logit - lse (NaN without a target),
+  // probe_lp [n_probe] = probe_logit - lse of the unmasked statistic
+  float* lse = nullptr; float* logprob = nullptr; float* probe_lp = nullptr;
+};
+int score_splits(int R, int V, int requested);            // requested <= 0: enough splits to fill the machine at this R
+int launch_score_logits(hipStream_t st, const ScoreArgs& a);   // 0, or -1 for an unsupported shape (nothing launched)
+void launch_score_merge(hipStream_t st, const ScoreArgs& a);
 
 }  // namespace wb

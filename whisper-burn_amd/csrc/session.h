@@ -103,4 +103,8 @@ int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_
 int session_align(wb_session* s, const int32_t* tokens, int32_t row_stride, const int32_t* lens, const int32_t* heads,
                   int32_t n_heads, int32_t n_prefix, int32_t drop_last, int32_t filter_width, int32_t* start_pos,
                   float* matrix, const int32_t* drop_last_rows);
+// wb_session_score (score.cpp); token_logprobs may be null (probes only)
+int session_score(wb_session* s, const int32_t* tokens, int32_t row_stride, const int32_t* lens, int32_t mask_until_len,
+                  const int32_t* probe_ids, int32_t n_probe, int32_t probe_pos, float* token_logprobs,
+                  float* probe_logprobs);
 }  // namespace wb

@@ -405,10 +405,14 @@ extern "C" int wb_beam_search(const wb_decode_params* p, int n_windows, int n_vo
 // token times (wb_waveform_to_token_times): each window's row is aligned on the session that decoded it
 struct TokenTimes { const int32_t* heads; int32_t n_heads, filter_width; float* win_times; float* stitched_times; };
 
+// token scores (wb_waveform_to_token_scores): each window's row is scored on the session that decoded it
+struct TokenScores { int32_t tok_no_speech; float* win_logprobs; float* stitched_logprobs; float* win_avg; float* win_no_speech; };
+
 static int waveform_to_tokens_impl(wb_model* m, const float* pcm, bool pcm_on_device, int64_t n, int sample_rate,
                                    const wb_decode_params* p, const uint8_t* is_special, int win_begin, int win_end,
                                    int32_t* win_tokens, int32_t row_stride, int32_t* win_lens, int32_t* stitched,
-                                   int64_t stitched_cap, int64_t* n_stitched, const TokenTimes* tt = nullptr) {
+                                   int64_t stitched_cap, int64_t* n_stitched, const TokenTimes* tt = nullptr,
+                                   const TokenScores* ts = nullptr) {
   WB_REQUIRE(m && pcm && p && is_special && win_tokens && win_lens, WB_ERR_ARG, "wb_waveform_to_tokens: null argument");
   wb::GpuTurn turn(m->device);   // (the sharded entry point calls this for its local windows and exchanges results outside the turn)
   WB_REQUIRE(p->padding >= 0 && p->padding < m->max_mel_frames(), WB_ERR_ARG, "bad padding");
@@ -460,12 +464,31 @@ static int waveform_to_tokens_impl(wb_model* m, const float* pcm, bool pcm_on_de
           }
         }
       }
+      if (rc == WB_OK && ts) {
+        const int32_t* rows = win_tokens + (size_t)b0 * row_stride;
+        const int32_t np = ts->tok_no_speech >= 0 ? 1 : 0;
+        std::vector<float> probe((size_t)nb);
+        float* lp = ts->win_logprobs + (size_t)b0 * row_stride;
+        rc = session_score(s, rows, row_stride, win_lens + b0, p->mask_until_len, &ts->tok_no_speech, np, 0, lp, probe.data());
+        for (int w = 0; rc == WB_OK && w < nb; w++) {
+          // Whisper's avg_logprob: the generated tokens (after the four prompt tokens), a final <|endoftext|> included
+          double sum = 0.0;
+          const int len = win_lens[b0 + w];
+          for (int l = 4; l < len; l++) sum += lp[(size_t)w * row_stride + l];
+          ts->win_avg[b0 + w] = len > 4 ? (float)(sum / (len - 4)) : std::nanf("");
+          ts->win_no_speech[b0 + w] = np ? std::exp(probe[w]) : std::nanf("");
+        }
+      }
       wb_session_free(s);
     }
     return rc;
   };
   for (int bi = 0; bi < n_batches; bi++) WB_TRY(run_batch(bi));
-  if (stitched && tt) {
+  if (stitched && ts) {
+    WB_REQUIRE(n_stitched && ts->stitched_logprobs, WB_ERR_ARG, "n_stitched / stitched_logprobs is null");
+    WB_TRY(wb_stitch_windows_times(win_tokens, row_stride, win_lens, n_local, p->max_n_offsets, p->min_n_overlaps, stitched,
+                                   stitched_cap, n_stitched, ts->win_logprobs, ts->stitched_logprobs));
+  } else if (stitched && tt) {
     WB_REQUIRE(n_stitched && tt->stitched_times, WB_ERR_ARG, "n_stitched / stitched_times is null");
     WB_TRY(wb_stitch_windows_times(win_tokens, row_stride, win_lens, n_local, p->max_n_offsets, p->min_n_overlaps, stitched,
                                    stitched_cap, n_stitched, tt->win_times, tt->stitched_times));
@@ -504,4 +527,19 @@ extern "C" int wb_waveform_to_token_times(wb_model* m, const float* pcm, int64_t
   const TokenTimes tt{heads, n_heads, filter_width, win_times, stitched_times};
   return waveform_to_tokens_impl(m, pcm, false, n, sample_rate, p, is_special, win_begin, win_end, win_tokens, row_stride,
                                  win_lens, stitched, stitched_cap, n_stitched, &tt);
+}
+
+extern "C" int wb_waveform_to_token_scores(wb_model* m, const float* pcm, int64_t n, int sample_rate,
+                                           const wb_decode_params* p, const uint8_t* is_special, int win_begin, int win_end,
+                                           int32_t* win_tokens, int32_t row_stride, int32_t* win_lens, int32_t* stitched,
+                                           int64_t stitched_cap, int64_t* n_stitched, int32_t tok_no_speech,
+                                           float* win_logprobs, float* stitched_logprobs, float* win_avg_logprob,
+                                           float* win_no_speech_prob) {
+  WB_REQUIRE(win_logprobs && win_avg_logprob && win_no_speech_prob && (stitched_logprobs || !stitched), WB_ERR_ARG,
+             "wb_waveform_to_token_scores: null score buffer");
+  WB_REQUIRE(!m || tok_no_speech < m->dims.n_vocab, WB_ERR_ARG, "wb_waveform_to_token_scores: no-speech token %d out of range",
+             tok_no_speech);
+  const TokenScores ts{tok_no_speech, win_logprobs, stitched_logprobs, win_avg_logprob, win_no_speech_prob};
+  return waveform_to_tokens_impl(m, pcm, false, n, sample_rate, p, is_special, win_begin, win_end, win_tokens, row_stride,
+                                 win_lens, stitched, stitched_cap, n_stitched, nullptr, &ts);
 }

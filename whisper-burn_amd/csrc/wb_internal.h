@@ -124,9 +124,16 @@ struct DecBlockW {
 // Device buffers of the token alignment (engine.cpp: run_align), grow-only like the rest of the workspace
 struct AlignBufs { DevMem tok_dev, heads_dev, stats, dtw_segs, trace, M, start; };
 
+// Device buffers of the token scoring (engine.cpp: run_score); `part` is vs x R float4 -- never R x V
+struct ScoreBufs {
+  DevMem i32, mask, part, f32;
+  std::vector<uint8_t> mask_host;         // the is_special bytes `mask` was built from (stateless entry: skip the re-upload)
+};
+
 // Grow-only device workspace shared by the forward passes of one owner (model scratch or session).
 struct Workspace {
   AlignBufs align;
+  ScoreBufs score;
   DevMem x1, x, h, qkv, att, hm, desc1, desc2, auxidx, segs, misc;
   // geometry the encoder descriptors on the device were built for: a transcription loop over equally shaped batches
   // (the common case) re-uses them instead of paying four uploads and a stream synchronisation per batch

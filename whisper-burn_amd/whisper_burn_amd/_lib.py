@@ -126,6 +126,19 @@ SIGNATURES = {
                                              c_float_p, c_float_p]),
     "wb_stitch_windows_times": (C.c_int, [c_int32_p, C.c_int32, c_int32_p, C.c_int, C.c_int, C.c_int, c_int32_p,
                                           C.c_int64, c_int64_p, c_float_p, c_float_p]),
+    "wb_score_tokens": (C.c_int, [C.c_void_p, c_int32_p, C.c_int, C.c_int, c_int32_p, c_float_p, C.c_int, c_uint8_p,
+                                  C.c_int32, c_int32_p, C.c_int32, C.c_int32, c_float_p, c_float_p]),
+    "wb_session_score": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_int32_p, C.c_int32, c_int32_p, C.c_int32,
+                                   C.c_int32, c_float_p, c_float_p]),
+    "wb_waveform_detect_language": (C.c_int, [C.c_void_p, c_float_p, C.c_int64, C.c_int, C.c_int32, C.c_int32, c_int32_p,
+                                              C.c_int32, C.c_int32, c_float_p, c_float_p, c_int32_p]),
+    "wb_waveform_to_token_scores": (C.c_int, [C.c_void_p, c_float_p, C.c_int64, C.c_int, C.POINTER(WbDecodeParams),
+                                              c_uint8_p, C.c_int, C.c_int, c_int32_p, C.c_int32, c_int32_p,
+                                              c_int32_p, C.c_int64, c_int64_p, C.c_int32, c_float_p, c_float_p,
+                                              c_float_p, c_float_p]),
+    "wb_logprob_gather": (C.c_int, [C.c_int, c_float_p, C.c_int32, C.c_int32, c_float_p, C.c_int32, c_float_p, c_uint8_p,
+                                    c_int32_p, c_int32_p, c_int32_p, C.c_int32, C.c_int32, c_float_p, c_float_p,
+                                    c_float_p]),
     "wb_first_repetition_end": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_repetition_period": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_find_repeated_tokens_index": (C.c_int, [c_int32_p, C.c_int64, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),

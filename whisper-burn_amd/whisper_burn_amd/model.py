@@ -70,6 +70,35 @@ def dtw_start_positions(x, device: int = 0) -> np.ndarray:
     return out
 
 
+def _u8p(a: Optional[np.ndarray]):
+    return a.ctypes.data_as(_lib.c_uint8_p) if a is not None else None
+
+
+def logprob_gather(h, E, target=None, mask=None, row_masked=None, probes=None, v_splits: int = 0, device: int = 0):
+    """The fused scoring kernels alone (wb_logprob_gather, a test hook): h [R, d], E [V, d] -> (logprob [R], lse [R],
+    probe_lp [n_probe]).  mask [V] of 0 / -inf applies to the rows with row_masked != 0; target[r] = -1: none;
+    probes: (row, id) pairs, scored unmasked."""
+    h, E = _f32(h), _f32(E)
+    R, d = h.shape
+    V = E.shape[0]
+    assert E.shape[1] == d
+    tg = _i32(target) if target is not None else None
+    mk = _f32(mask) if mask is not None else None
+    rm = np.ascontiguousarray(row_masked, dtype=np.uint8) if row_masked is not None else None
+    pr = _i32(np.asarray(probes, dtype=np.int32).reshape(-1, 2)) if probes is not None and len(probes) else None
+    n_probe = len(pr) if pr is not None else 0
+    prow = _i32(pr[:, 0]) if pr is not None else None
+    pid = _i32(pr[:, 1]) if pr is not None else None
+    lp = np.full(R, np.nan, dtype=np.float32)
+    lse = np.full(R, np.nan, dtype=np.float32)
+    plp = np.full(max(n_probe, 1), np.nan, dtype=np.float32)
+    check(_lib.load().wb_logprob_gather(device, _fp(h), R, d, _fp(E), V, _fp(mk) if mk is not None else None, _u8p(rm),
+                                        _ip(tg) if tg is not None else None, _ip(prow) if pr is not None else None,
+                                        _ip(pid) if pr is not None else None, n_probe, v_splits, _fp(lp), _fp(lse),
+                                        _fp(plp)))
+    return lp, lse, plp[:n_probe]
+
+
 def special_mask_bytes(whisper: "Whisper", is_special) -> np.ndarray:
     """uint8 [n_vocab] for the C side, which reads exactly n_vocab bytes.  The reference adds a [vocab_size] mask to
     [.., n_vocab] logits (transcribe.rs:243-275) and panics when the tokenizer's vocabulary and the model's differ; a
@@ -342,6 +371,26 @@ class Whisper:
                                           _ip(pos), _fp(mat) if mat is not None else None))
         return (pos, mat) if return_matrix else pos
 
+    def score_tokens(self, tokens, encoder_output, lens=None, is_special=None, mask_until_len: int = 0,
+                     probe_ids=None, probe_pos: int = 0):
+        """Per-token log-probabilities of finished rows (wb_score_tokens): tokens [n, L] (+ lens) or a list of rows,
+        encoder_output [n, C, d] -> token_logprobs [n, L]: entry l = log-prob of tokens[l] given tokens[:l] (NaN at entry
+        0 and past a row's len), under the special mask `is_special` while l <= mask_until_len.  With probe_ids also
+        returns probe_logprobs [n, n_probe]: the unmasked log-probs of those ids at position probe_pos."""
+        tokens, lens = _rows_arg(tokens, lens)
+        enc = _f32(encoder_output)
+        n, L = tokens.shape
+        assert enc.shape[0] == n and enc.shape[2] == self.dims["n_text_state"]
+        mk = special_mask_bytes(self, is_special) if is_special is not None else None
+        pid = _i32(probe_ids) if probe_ids is not None else None
+        npb = len(pid) if pid is not None else 0
+        lp = np.full((n, L), np.nan, dtype=np.float32)
+        plp = np.full((n, max(npb, 1)), np.nan, dtype=np.float32)
+        check(_lib.load().wb_score_tokens(self._h, _ip(tokens), n, L, _ip(lens), _fp(enc), enc.shape[1], _u8p(mk),
+                                          mask_until_len, _ip(pid) if pid is not None else None, npb, probe_pos,
+                                          _fp(lp), _fp(plp) if npb else None))
+        return (lp, plp[:, :npb]) if pid is not None else lp
+
     def forward(self, mel, tokens) -> np.ndarray:
         mel = _f32(mel)
         tokens = _i32(tokens)
@@ -480,6 +529,73 @@ def waveform_to_token_times(whisper: Whisper, st: SpecialTokens, waveform, sampl
             [win_times[i, :win_lens[i]].copy() for i in range(n)])
 
 
+def waveform_to_token_scores(whisper: Whisper, st: SpecialTokens, waveform, sample_rate: int = 16000,
+                             beam_size: int = 5, max_depth: int = 100, params: Optional[WbDecodeParams] = None,
+                             no_speech: Optional[int] = None):
+    """waveform_to_tokens + token log-probabilities (wb_waveform_to_token_scores).
+
+    Returns a dict: tokens / logprobs (the stitched stream), win_tokens / win_logprobs (per window; NaN at entry 0),
+    avg_logprob [n_windows] (mean over the generated tokens of the window) and no_speech_prob [n_windows] (NaN when the
+    vocabulary has no no-speech token: `no_speech`, default st.no_speech, is -1)."""
+    lib = _lib.load()
+    if no_speech is None:
+        no_speech = st.no_speech
+    wav = _f32(waveform).reshape(-1)
+    p = params or decode_params(st, beam_size, max_depth)
+    wlen = max_waveform_samples(whisper.max_mel_frames() - p.padding)
+    starts, _ = window_extents(len(wav), sample_rate, wlen, p.overlap_seconds)
+    n = len(starts)
+    n_win = max(n, 1)
+    stride = 4 + p.max_depth + 4
+    win_tokens = np.zeros((n_win, stride), dtype=np.int32)
+    win_lens = np.zeros(n_win, dtype=np.int32)
+    win_lp = np.full((n_win, stride), np.nan, dtype=np.float32)
+    cap = n_win * stride
+    stitched = np.zeros(cap, dtype=np.int32)
+    stitched_lp = np.full(cap, np.nan, dtype=np.float32)
+    avg = np.full(n_win, np.nan, dtype=np.float32)
+    nsp = np.full(n_win, np.nan, dtype=np.float32)
+    n_st = C.c_int64(0)
+    mask = special_mask_bytes(whisper, st.is_special)
+    check(lib.wb_waveform_to_token_scores(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p),
+                                          mask.ctypes.data_as(_lib.c_uint8_p), 0, -1, _ip(win_tokens), stride,
+                                          _ip(win_lens), _ip(stitched), cap, C.byref(n_st), int(no_speech), _fp(win_lp),
+                                          _fp(stitched_lp), _fp(avg), _fp(nsp)))
+    return dict(tokens=stitched[:n_st.value].tolist(), logprobs=stitched_lp[:n_st.value].copy(),
+                win_tokens=[win_tokens[i, :win_lens[i]].tolist() for i in range(n)],
+                win_logprobs=[win_lp[i, :win_lens[i]].copy() for i in range(n)],
+                avg_logprob=avg[:n].copy(), no_speech_prob=nsp[:n].copy())
+
+
+def detect_language(whisper: Whisper, st_or_ids, waveform, sample_rate: int = 16000, sot: Optional[int] = None,
+                    padding: int = 10, max_windows: int = 1):
+    """Whisper's detect_language over the first `max_windows` windows (0: all; wb_waveform_detect_language).
+    st_or_ids: a SpecialTokens (its `language_ids` and start_of_transcript are used), or a sequence of language token
+    ids (then `sot` is required).  Returns (best index into the ids, mean_probs [n_lang], win_probs [W, n_lang])."""
+    if hasattr(st_or_ids, "start_of_transcript"):
+        ids = st_or_ids.language_ids
+        if len(ids) == 0:
+            raise ValueError("the tokenizer has no language tokens: language detection needs a multilingual vocabulary")
+        sot = st_or_ids.start_of_transcript if sot is None else sot
+    else:
+        ids = st_or_ids
+    if sot is None:
+        raise ValueError("detect_language: sot (the start-of-transcript id) is required with a plain id list")
+    ids = _i32(list(ids))
+    wav = _f32(waveform).reshape(-1)
+    wlen = max_waveform_samples(whisper.max_mel_frames() - padding)
+    dp = WbDecodeParams()
+    _lib.load().wb_decode_params_default(C.byref(dp))        # the C side cuts its windows with the default overlap
+    starts, _ = window_extents(len(wav), sample_rate, wlen, dp.overlap_seconds)
+    W = len(starts) if max_windows <= 0 else min(max_windows, len(starts))
+    win = np.zeros((max(W, 1), len(ids)), dtype=np.float32)
+    mean = np.zeros(len(ids), dtype=np.float32)
+    best = C.c_int32(-1)
+    check(_lib.load().wb_waveform_detect_language(whisper._h, _fp(wav), len(wav), sample_rate, padding, int(sot), _ip(ids),
+                                                  len(ids), max_windows, _fp(win), _fp(mean), C.byref(best)))
+    return int(best.value), mean, win[:W]
+
+
 def waveform_to_text(whisper: Whisper, bpe, lang, waveform, sample_rate: int = 16000):
     """transcribe.rs:23-29 shape: returns (text, tokens).  `bpe` must offer
     `special_tokens(lang) -> SpecialTokens` and `decode(tokens, skip_special) -> str`
@@ -574,6 +690,33 @@ class Session:
                                            n_prefix, drop_last, filter_width, _ip(pos),
                                            _fp(mat) if mat is not None else None))
         return (pos, mat) if return_matrix else pos
+
+    def score(self, tokens, lens=None, mask_until_len: int = 0, probe_ids=None, probe_pos: int = 0):
+        """Per-token log-probabilities of one row per window (wb_session_score) on the session's cached cross K/V:
+        token_logprobs [W, L] as Whisper.score_tokens; the mask is the one of set_special_mask.  With probe_ids also
+        returns probe_logprobs [W, n_probe] (unmasked, at position probe_pos)."""
+        tokens, lens = _rows_arg(tokens, lens)
+        W, L = tokens.shape
+        assert W == self.n_windows
+        pid = _i32(probe_ids) if probe_ids is not None else None
+        npb = len(pid) if pid is not None else 0
+        lp = np.full((W, L), np.nan, dtype=np.float32)
+        plp = np.full((W, max(npb, 1)), np.nan, dtype=np.float32)
+        check(_lib.load().wb_session_score(self._h, _ip(tokens), L, _ip(lens), mask_until_len,
+                                           _ip(pid) if pid is not None else None, npb, probe_pos, _fp(lp),
+                                           _fp(plp) if npb else None))
+        return (lp, plp[:, :npb]) if pid is not None else lp
+
+    def detect_language(self, sot: int, lang_ids):
+        """Language probabilities of every window of the session: softmax over `lang_ids` of the distribution after
+        [sot] (Whisper's detect_language) -> (argmax of the mean over the windows, mean_probs, win_probs [W, n_lang])."""
+        ids = _i32(list(lang_ids))
+        _, plp = self.score(np.full((self.n_windows, 1), sot, dtype=np.int32), probe_ids=ids, probe_pos=0)
+        z = plp.astype(np.float64)
+        e = np.exp(z - z.max(axis=1, keepdims=True))
+        win = e / e.sum(axis=1, keepdims=True)
+        mean = win.mean(axis=0)
+        return int(np.argmax(mean)), mean.astype(np.float32), win.astype(np.float32)
 
     def close(self):
         if self._h:

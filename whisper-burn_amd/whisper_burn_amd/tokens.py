@@ -14,6 +14,11 @@ from dataclasses import dataclass
 import numpy as np
 
 
+LANGUAGES = ("en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk el ms cs ro da hu ta no th ur hr bg lt la "
+             "mi ml cy sk te fa lv bn sr az sl kn et mk br eu is hy ne mn bs kk sq sw gl mr pa si km sn yo so af oc ka be "
+             "tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my bo tl mg as tt ln ha ba jw su").split()   # token.rs:50-60
+
+
 @dataclass
 class SpecialTokens:
     start_of_transcript: int
@@ -23,6 +28,8 @@ class SpecialTokens:
     end_of_text: int
     is_special: np.ndarray      # uint8 [V]: 1 where tokenizer.decode([id], skip_special=True) == ""
     start_of_prev: int = -1     # <|startofprev|> (transcribe.rs:181); only the optional prompt-conditioning mode uses it
+    language_ids: tuple = ()    # every language token of the vocabulary, ascending (empty: English-only); detect_language
+    no_speech: int = -1         # <|nospeech|> (<|nocaptions|> in the original vocabulary files); -1: none
 
     @staticmethod
     def for_vocab(n_vocab: int, language_index: int = 0) -> "SpecialTokens":
@@ -32,19 +39,22 @@ class SpecialTokens:
             eot, sot = 50256, 50257
             lang0, transcribe, notimestamps = 50258, 50358, 50362
             sop = 50360
+            langs, nsp = (), 50361           # the .en vocabulary keeps the slots, the checkpoint knows one language
         elif n_vocab == 51865:
             eot, sot = 50257, 50258
             lang0, transcribe, notimestamps = 50259, 50359, 50363
             sop = 50361
+            langs, nsp = tuple(range(50259, 50358)), 50362   # 99 slots between sot and <|translate|>
         else:
             assert n_vocab >= 32
             eot = n_vocab - 16
             sot, lang0, transcribe, notimestamps = eot + 1, eot + 2, eot + 4, eot + 6
             sop = eot + 5
             language_index = 0
+            langs, nsp = (eot + 2, eot + 3), -1     # two language slots (en, zh), no no-speech token
         is_special = np.zeros(n_vocab, dtype=np.uint8)
         is_special[eot:] = 1
-        return SpecialTokens(sot, lang0 + language_index, transcribe, notimestamps, eot, is_special, sop)
+        return SpecialTokens(sot, lang0 + language_index, transcribe, notimestamps, eot, is_special, sop, langs, nsp)
 
 
 # ---- tokenizer integration (src/token.rs) -------------------------------------------------------------------
@@ -95,4 +105,18 @@ class TokenizerAdapter:
         mask = np.array([1 if self.is_special(t) else 0 for t in range(self.vocab_size())], dtype=np.uint8)
         sop = self.special_token(special_token_name("startofprev"))
         return SpecialTokens(ids["startoftranscript"], ids["language"], ids["transcribe"], ids["notimestamps"],
-                             ids["endoftext"], mask, -1 if sop is None else int(sop))
+                             ids["endoftext"], mask, -1 if sop is None else int(sop),
+                             tuple(t for _, t in self.language_tokens()), self.no_speech_token())
+
+    def language_tokens(self):
+        """(abbreviation, id) of every language token the tokenizer knows, in LANGUAGES order."""
+        known = [(name, self.special_token(special_token_name("language", name))) for name in LANGUAGES]
+        return [(name, int(t)) for name, t in known if t is not None]
+
+    def no_speech_token(self) -> int:
+        """<|nospeech|>, or its name in the original vocabulary files, <|nocaptions|>; -1: none."""
+        for name in (special_token_name("nospeech"), "<|nocaptions|>"):
+            t = self.special_token(name)
+            if t is not None:
+                return int(t)
+        return -1

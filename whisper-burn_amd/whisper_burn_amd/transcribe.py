@@ -13,6 +13,14 @@ written to `<transcription file>` (main.rs:151-154).  Exit code 1 with the refer
 `{"id", "text", "start"}` with the token's start time in seconds (2 decimals), from the decoder's cross-attention
 alignment (wb_waveform_to_token_times).  Without the flag the output is what it always was.
 
+`--scores PATH` additionally writes one JSON object per line for every stitched non-special token, `{"id", "text",
+"logprob"}`, and then one per window, `{"window", "avg_logprob", "no_speech_prob"}` (wb_waveform_to_token_scores;
+`no_speech_prob` is null when the tokenizer has no no-speech token, and so is any value that is not finite).  Together
+with `--token-times` the audio is decoded once per option: each is one library call that decodes and then aligns / scores.
+
+`<lang>` = `auto` detects the language from the first windows of the audio (wb_waveform_detect_language over the
+language tokens the tokenizer knows) and prints it before decoding; a tokenizer without language tokens is an error.
+
 One addition: with `WHISPER_HIP_RESAMPLE=1` in the environment a mono WAV of another sample rate (the bundled
 22 050 Hz audio.wav, which the reference sends through `sox`, README.md:69-74) is resampled to 16 kHz on the GPU
 (wb_resample_dev) instead of being rejected.
@@ -22,9 +30,7 @@ from __future__ import annotations
 import os
 import sys
 
-LANGUAGES = ("en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk el ms cs ro da hu ta no th ur hr bg lt la "
-             "mi ml cy sk te fa lv bn sr az sl kn et mk br eu is hy ne mn bs kk sq sw gl mr pa si km sn yo so af oc ka be "
-             "tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my bo tl mg as tt ln ha ba jw su").split()   # token.rs:50-60
+from .tokens import LANGUAGES  # noqa: E402  (token.rs:50-60)
 
 
 def main(argv=None) -> int:
@@ -35,22 +41,25 @@ def main(argv=None) -> int:
     model_name, wav_file, lang, text_file = argv[1:5]
     frontend = None
     times_file = None
+    scores_file = None
     extra = argv[5:]
     usage = (f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference] "
-             f"[--token-times PATH]")
+             f"[--token-times PATH] [--scores PATH]")
     while extra:                                # (other trailing arguments are ignored, as before)
-        if extra[0] in ("--frontend", "--token-times"):
+        if extra[0] in ("--frontend", "--token-times", "--scores"):
             if len(extra) < 2 or (extra[0] == "--frontend" and extra[1] not in ("fft", "reference")):
                 print(usage, file=sys.stderr)
                 return 1
             if extra[0] == "--frontend":
                 frontend = extra[1]
+            elif extra[0] == "--scores":
+                scores_file = extra[1]
             else:
                 times_file = extra[1]
             extra = extra[2:]
         else:
             extra = extra[1:]
-    if lang not in LANGUAGES:
+    if lang != "auto" and lang not in LANGUAGES:
         print(f"Invalid language abbreviation: {lang}", file=sys.stderr)
         return 1
     import whisper_burn_amd as wb
@@ -73,6 +82,14 @@ def main(argv=None) -> int:
     except Exception as e:                                                 # noqa: BLE001
         print(f"Failed to load tokenizer: {e}", file=sys.stderr)
         return 1
+    known, sot = [], None
+    if lang == "auto":
+        known = bpe.language_tokens()
+        sot = bpe.special_token("<|startoftranscript|>")
+        if not known or sot is None:
+            print("Cannot detect the language: the tokenizer has no language tokens (an English-only vocabulary); "
+                  "name the language instead of 'auto'", file=sys.stderr)
+            return 1
     print("Loading model...")
     try:
         if os.path.isdir(model_name):
@@ -92,13 +109,28 @@ def main(argv=None) -> int:
         def decode(self, tokens, skip_special):
             return bpe.decode(tokens, skip_special)
 
+    if lang == "auto":
+        try:
+            best, probs, _ = wb.detect_language(whisper, [t for _, t in known], waveform, sample_rate, sot=int(sot),
+                                                max_windows=3)
+        except Exception as e:                                             # noqa: BLE001
+            print(f"Error during language detection: {e}", file=sys.stderr)
+            return 1
+        lang = known[best][0]
+        print(f"Detected language: {lang} (p = {float(probs[best]):.3f})")
+
     token_times = None
+    scores = None
     try:
-        if times_file is None:
+        if times_file is None and scores_file is None:
             text, _tokens = wb.waveform_to_text(whisper, Bpe(), lang, waveform, sample_rate)
         else:
             st = bpe.special_tokens(lang)
-            _tokens, token_times, _, _ = wb.waveform_to_token_times(whisper, st, waveform, sample_rate)
+            if times_file is not None:
+                _tokens, token_times, _, _ = wb.waveform_to_token_times(whisper, st, waveform, sample_rate)
+            if scores_file is not None:
+                scores = wb.waveform_to_token_scores(whisper, st, waveform, sample_rate, no_speech=st.no_speech)
+                _tokens = scores["tokens"]
             text = bpe.decode(_tokens, True)
     except Exception as e:                                                 # noqa: BLE001
         print(f"Error during transcription: {e}", file=sys.stderr)
@@ -120,6 +152,23 @@ def main(argv=None) -> int:
                     fh.write(json.dumps({"id": int(tok), "text": bpe.decode([tok], True), "start": round(float(t), 2)}) + "\n")
         except OSError as e:
             print(f"Error writing token times file: {e}", file=sys.stderr)
+            return 1
+    if scores_file is not None:
+        import json
+        import math
+
+        def num(x):
+            return float(x) if math.isfinite(float(x)) else None         # (NaN: no value; -inf cannot be JSON either)
+        try:
+            with open(scores_file, "w") as fh:
+                for tok, lp in zip(scores["tokens"], scores["logprobs"]):
+                    if st.is_special[tok]:
+                        continue
+                    fh.write(json.dumps({"id": int(tok), "text": bpe.decode([tok], True), "logprob": num(lp)}) + "\n")
+                for w, (a, n) in enumerate(zip(scores["avg_logprob"], scores["no_speech_prob"])):
+                    fh.write(json.dumps({"window": w, "avg_logprob": num(a), "no_speech_prob": num(n)}) + "\n")
+        except OSError as e:
+            print(f"Error writing scores file: {e}", file=sys.stderr)
             return 1
     print("Transcription finished.")
     return 0
