@@ -468,6 +468,89 @@ int wb_logprob_gather(int device, const float* h, int32_t R, int32_t d, const fl
                       const int32_t* probe_id, int32_t n_probe, int32_t v_splits, float* logprob, float* lse,
                       float* probe_lp);
 
+/* ---- temperature sampling and Whisper's decode fallback (an extension: the reference has beam search only) -----------
+ * The draw (sample.hip): token = argmax_v [(x_v + mask_v - M) / T + g_v] by (key descending, id ascending), with
+ * g_v = -logf(-logf(u_v)), u_v = ((word >> 9) + 0.5) 2^-23 and word = output (v & 3) of Philox4x32-10 under
+ * key = (seed low 32, seed high 32), counter = (v >> 2, position, stream, attempt).  position: the index in the token row of
+ * the token being drawn.  A sampled token is therefore a pure function of its logits row and five integers: it does not
+ * depend on the launch shape, on the rows that share the batch or on the rank that decodes the window.  Recorded with each
+ * token: log_softmax of the (masked) logits -- not of logits / T -- as Whisper's sum_logprobs. */
+typedef struct wb_sample_params {
+  float temperature;            /* > 0 */
+  int32_t best_of;              /* samples per window, 1 .. max_beams of the session */
+  uint64_t seed;
+  int32_t attempt;              /* index of the temperature in the fallback list: the fourth counter word */
+} wb_sample_params;
+void wb_sample_params_default(wb_sample_params* p);      /* 1.0, 5, 0, 0 */
+/* Back to step 0 over the same encoded window batch: the encoder output and the cached cross K/V stay, so another decode
+ * costs decode steps only. */
+int wb_session_rewind(wb_session* s);
+/* Debug / tests: the number of captured step graphs the session holds. */
+int wb_session_graph_count(const wb_session* s);
+/* Debug / tests: step graphs captured over the session's life (a replayed graph does not count). */
+int64_t wb_session_graph_captures(const wb_session* s);
+/* best_of independent sampled sequences per window from `prompt`, on a fresh or rewound session; the draw and the row
+ * bookkeeping run on the device, chunks of steps replay as one graph (the same graph for every temperature and seed).
+ * active [W] (NULL = all): windows with active[w] == 0 are not decoded and nothing of theirs is written.
+ * stream_ids [W] (NULL = w * best_of): sample j of window w draws from stream stream_ids[w] + j.
+ * out_tokens / out_lens: per window the sample with the largest sum_logprob / n_text (n_text = generated tokens without a
+ * final end-of-text; f64; the first of equal maxima; n_text == 0 ranks -inf), prompt included.  out_sum_logprob
+ * [W][best_of] f64 and out_best [W] are optional.  p supplies max_depth, mask_until_len and tok_end_of_text.
+ * Errors with nothing launched: temperature <= 0 or not finite, best_of outside 1 .. max_beams, row_stride <
+ * prompt_len + max_depth, a token outside the vocabulary -> WB_ERR_ARG; the special mask needed and not set, or a session
+ * that is not at step 0 -> WB_ERR_STATE. */
+int wb_session_decode_sample(wb_session* s, const wb_decode_params* p, const wb_sample_params* sp, const int32_t* prompt,
+                             int32_t prompt_len, const uint8_t* active, const int32_t* stream_ids, int32_t* out_tokens,
+                             int32_t row_stride, int32_t* out_lens, double* out_sum_logprob, int32_t* out_best);
+
+/* Debug / parity: every sample of the last wb_session_decode_sample on this session -- the generated tokens (without the
+ * prompt) of sample j of window w at tokens[(w * best_of + j) * row_stride], lens[w * best_of + j] of them (-1: the window
+ * was not active).  row_stride >= the call's max_depth. */
+int wb_session_last_samples(wb_session* s, int32_t* tokens, int32_t row_stride, int32_t* lens);
+
+enum { WB_FALLBACK_MAX_TEMPERATURES = 8 };
+enum { WB_FALLBACK_ACCEPT = 0, WB_FALLBACK_RETRY = 1, WB_FALLBACK_NO_SPEECH = 2 };
+typedef struct wb_fallback_params {
+  float temperatures[WB_FALLBACK_MAX_TEMPERATURES];   /* 0, 0.2, 0.4, 0.6, 0.8, 1.0; the first must be 0 (the ordinary decode) */
+  int32_t n_temperatures;
+  int32_t best_of;                       /* 5 */
+  float logprob_threshold;               /* -1.0   (NaN: rule off) */
+  float no_speech_threshold;             /* 0.6    (NaN: rule off) */
+  float compression_ratio_threshold;     /* 2.4    (NaN: rule off) */
+  uint64_t seed;
+  int32_t tok_no_speech;                 /* -1: the no-speech rule is off */
+} wb_fallback_params;
+void wb_fallback_params_default(wb_fallback_params* p);
+/* Whisper's decode_with_fallback and the skip test of transcribe, host only: retry when ratio >
+ * compression_ratio_threshold or avg_logprob < logprob_threshold, unless no_speech_prob > no_speech_threshold; no speech
+ * when no_speech_prob > no_speech_threshold and (avg_logprob < logprob_threshold, or that rule is off).  A NaN input to an
+ * enabled rule fails it.  Returns WB_FALLBACK_ACCEPT / _RETRY / _NO_SPEECH. */
+int wb_fallback_decide(const wb_fallback_params* fp, float avg_logprob, float no_speech_prob, float ratio);
+/* Compression ratio of one window's generated tokens, computed by the caller (text lives on its side of the boundary). */
+typedef double (*wb_ratio_fn)(void* user, const int32_t* tokens, int32_t n);
+/* wb_waveform_to_tokens with the fallback: per window batch the ordinary decode (p->beam_size) is attempt 0; the scoring
+ * pass on the same session gives avg_logprob (entries [4, len)) and the no-speech probability; windows that must retry are
+ * decoded again by wb_session_decode_sample at temperatures[1], [2], ... (attempt i, stream = global window index *
+ * best_of) after a rewind -- no re-encode -- and scored again, until they pass or the list ends (such a window keeps its
+ * last row, status 1).  Windows of status 2 are left out of the stitch; their rows are still returned.  ratio NULL: the
+ * compression-ratio rule is off and win_ratio is NaN.  Per-window outputs [n_local]: win_temperature, win_status,
+ * win_avg_logprob, win_no_speech_prob, win_ratio, win_attempts.  With every rule off the rows and the stitched stream are
+ * wb_waveform_to_tokens' bit for bit, after one attempt per window. */
+int wb_waveform_to_tokens_fallback(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                                   const uint8_t* is_special, int win_begin, int win_end, int32_t* win_tokens,
+                                   int32_t row_stride, int32_t* win_lens, int32_t* stitched, int64_t stitched_cap,
+                                   int64_t* n_stitched, const wb_fallback_params* fp, wb_ratio_fn ratio, void* user,
+                                   float* win_temperature, int32_t* win_status, float* win_avg_logprob,
+                                   float* win_no_speech_prob, float* win_ratio, int32_t* win_attempts);
+/* Test hook: the draw alone (the device function of the chain kernel) on caller data in host memory.  logits [R][ld]
+ * (ld >= V); mask [V] (0 / -inf) applies to the rows with row_masked[r] != 0 (both NULL: no mask); row_stats [R][2] = the
+ * row maximum and log-sum-exp under the row's mask; stream / position [R].  out_token / out_logprob [R]; a row with a NaN
+ * logit or without a finite key gives eot, log-prob 0 and *out_err = 1.  `device` only hosts the buffers. */
+int wb_sample_rows(int device, const float* logits, int32_t R, int32_t ld, int32_t V, const float* mask,
+                   const uint8_t* row_masked, const float* row_stats, float temperature, uint64_t seed, int32_t attempt,
+                   const int32_t* stream, const int32_t* position, int32_t eot, int32_t* out_token, float* out_logprob,
+                   int32_t* out_err);
+
 /* The reference's retired greedy decoder kept its repetition detectors (transcribe.rs:385-447, dead code there):
  *   wb_first_repetition_end        :385-393   (period > n, a usize underflow panic there -> WB_ERR_ARG)
  *   wb_repetition_period           :395-417   returns the period, 0 for None

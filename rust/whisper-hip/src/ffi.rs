@@ -50,6 +50,31 @@ pub struct wb_decode_params {
     pub tok_end_of_text: i32,
 }
 
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct wb_sample_params {
+    pub temperature: c_float,
+    pub best_of: i32,
+    pub seed: u64,
+    pub attempt: i32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct wb_fallback_params {
+    pub temperatures: [c_float; 8],
+    pub n_temperatures: i32,
+    pub best_of: i32,
+    pub logprob_threshold: c_float,
+    pub no_speech_threshold: c_float,
+    pub compression_ratio_threshold: c_float,
+    pub seed: u64,
+    pub tok_no_speech: i32,
+}
+
+/// Compression ratio of one window's generated tokens, computed on the caller's side (it owns the tokenizer).
+pub type wb_ratio_fn = Option<unsafe extern "C" fn(user: *mut c_void, tokens: *const i32, n: i32) -> c_double>;
+
 pub const WB_OK: c_int = 0;
 pub const WB_ERR_ARG: c_int = -1;
 pub const WB_ERR_SHAPE: c_int = -2;
@@ -128,6 +153,14 @@ extern "C" {
                              mask: *const c_float, row_masked: *const u8, target: *const i32, probe_row: *const i32,
                              probe_id: *const i32, n_probe: i32, v_splits: i32, logprob: *mut c_float, lse: *mut c_float,
                              probe_lp: *mut c_float) -> c_int;
+    pub fn wb_session_rewind(s: *mut wb_session) -> c_int;
+    pub fn wb_session_graph_count(s: *const wb_session) -> c_int;
+    pub fn wb_session_graph_captures(s: *const wb_session) -> i64;
+    pub fn wb_session_last_samples(s: *mut wb_session, tokens: *mut i32, row_stride: i32, lens: *mut i32) -> c_int;
+    pub fn wb_sample_rows(device: c_int, logits: *const c_float, R: i32, ld: i32, V: i32, mask: *const c_float,
+                          row_masked: *const u8, row_stats: *const c_float, temperature: c_float, seed: u64, attempt: i32,
+                          stream: *const i32, position: *const i32, eot: i32, out_token: *mut i32,
+                          out_logprob: *mut c_float, out_err: *mut i32) -> c_int;
     pub fn wb_session_begin(m: *mut wb_model, pcm: *const c_float, n_pcm: i64, starts: *const i64, lens: *const i64,
                             n_windows: c_int, max_beams: c_int, padding: c_int, out: *mut *mut wb_session) -> c_int;
     pub fn wb_session_set_special_mask(s: *mut wb_session, is_special: *const u8) -> c_int;
@@ -153,6 +186,27 @@ extern "C" {
                                          stitched: *mut i32, stitched_cap: i64, n_stitched: *mut i64) -> c_int;
     pub fn wb_last_error() -> *const c_char;
     pub fn wb_version() -> *const c_char;
+}
+
+// Temperature sampling and the decode fallback: the entry points whose arguments are the parameter structs / the callback
+// type defined above (their own block: tests/test_rust_shim.py type-checks the first block against the header's scalars).
+extern "C" {
+    pub fn wb_sample_params_default(p: *mut wb_sample_params);
+    pub fn wb_session_decode_sample(s: *mut wb_session, p: *const wb_decode_params, sp: *const wb_sample_params,
+                                    prompt: *const i32, prompt_len: i32, active: *const u8, stream_ids: *const i32,
+                                    out_tokens: *mut i32, row_stride: i32, out_lens: *mut i32,
+                                    out_sum_logprob: *mut c_double, out_best: *mut i32) -> c_int;
+    pub fn wb_fallback_params_default(p: *mut wb_fallback_params);
+    pub fn wb_fallback_decide(fp: *const wb_fallback_params, avg_logprob: c_float, no_speech_prob: c_float,
+                              ratio: c_float) -> c_int;
+    pub fn wb_waveform_to_tokens_fallback(m: *mut wb_model, pcm: *const c_float, n: i64, sample_rate: c_int,
+                                          p: *const wb_decode_params, is_special: *const u8, win_begin: c_int,
+                                          win_end: c_int, win_tokens: *mut i32, row_stride: i32, win_lens: *mut i32,
+                                          stitched: *mut i32, stitched_cap: i64, n_stitched: *mut i64,
+                                          fp: *const wb_fallback_params, ratio: wb_ratio_fn, user: *mut c_void,
+                                          win_temperature: *mut c_float, win_status: *mut i32,
+                                          win_avg_logprob: *mut c_float, win_no_speech_prob: *mut c_float,
+                                          win_ratio: *mut c_float, win_attempts: *mut i32) -> c_int;
 }
 
 /// The exchange of the sharded path: `send` = this rank's bytes, `recv` = world x bytes_per_rank bytes in rank order.

@@ -172,6 +172,51 @@ struct BeamChainArgs {
 };
 void launch_dec_beam_update(hipStream_t st, const BeamChainArgs& a);
 
+// ---- device-chained temperature sampling (sample.hip, sample_chain.cpp) ------------------------------------------
+// Independent rows (slot = active window ordinal * best_of + j), one Gumbel-max draw per row and step on a counter-based
+// generator: the bookkeeping kernel behind the logits tail draws the row's token from the step's logits, records it and
+// prepares the row for the next step.  Everything a call may vary without changing the launch sequence -- 1 / T, seed,
+// attempt, the rows' stream ids -- lives in the control block, so one captured graph serves every temperature and seed.
+enum { SC_NDONE = 0, SC_ALLDONE = 1, SC_ERR = 2, SC_NROWS = 3, SC_BEST_OF = 4, SC_ATTEMPT = 5, SC_SEED_LO = 6, SC_SEED_HI = 7,
+       SC_INVT = 8, SC_HDR = 16 };   // header ints of the control block ([SC_INVT]: the bits of the f32 1 / T)
+struct SampleChainLayout {
+  int S = 0, W = 0, max_depth = 0;
+  // int offsets: stream / fin / ngen [S], win_fin [W] (finished rows per window); then doubles sum [S] (8-byte aligned);
+  // then the generated tokens int[S][max_depth]
+  int stream = 0, fin = 0, ngen = 0, win_fin = 0, sum = 0, tokens = 0, total_ints = 0;
+};
+inline SampleChainLayout make_sample_layout(int S, int W, int max_depth) {
+  SampleChainLayout b;
+  b.S = S; b.W = W; b.max_depth = max_depth;
+  b.stream = SC_HDR; b.fin = b.stream + S; b.ngen = b.fin + S; b.win_fin = b.ngen + S;
+  b.sum = (b.win_fin + W + 1) & ~1;
+  b.tokens = b.sum + 2 * S;
+  b.total_ints = b.tokens + S * max_depth;
+  return b;
+}
+struct SampleChainArgs {
+  int* ctl = nullptr; SampleChainLayout sl;
+  const float* logits = nullptr; int V = 0;                            // the step's unmasked logits [S][V]
+  const float* mask = nullptr; int use_mask = 0;                       // the step's special mask (added when use_mask)
+  const float* row_stats = nullptr;                                    // [S][2]: row maximum and log-sum-exp under that mask
+  int* state = nullptr; StepLayout lay;                                // the step state block (device memory), updated in place
+  int eot = 0;
+  // the next step's position tables and embedding rows (what dec_prepare_kernel does for a host-driven step)
+  int* tabs = nullptr; int Lmax = 0; const float* E = nullptr; const float* pos = nullptr; int d = 0; float* x = nullptr;
+};
+void launch_dec_sample_update(hipStream_t st, const SampleChainArgs& a, int n_rows);
+// test hook (wb_sample_rows): the draw alone, one block per row, on caller data in device memory
+struct SampleRowsArgs {
+  const float* logits = nullptr; int R = 0, ld = 0, V = 0;
+  const float* mask = nullptr; const uint8_t* row_masked = nullptr;    // mask [V] added to the rows with row_masked[r] != 0
+  const float* row_stats = nullptr;                                    // [R][2]
+  float inv_t = 1.f; uint32_t seed_lo = 0, seed_hi = 0, attempt = 0;
+  const int32_t* stream = nullptr; const int32_t* position = nullptr;  // [R]
+  int eot = 0;
+  int32_t* out_token = nullptr; float* out_logprob = nullptr; int32_t* out_err = nullptr;   // [R], [R], one word
+};
+void launch_sample_rows(hipStream_t st, const SampleRowsArgs& a);
+
 // ---- fused small-batch sublayer kernels (decode_fused.hip) ----------------------------------------------
 // Common prologue of both: x = x_in + (pbias + sum_s pend[s]) (KSp planes of [S][d]; KSp = 0: none), block 0
 // writes x to x_out, then LayerNorm(ln_g, ln_b, ln_eps).

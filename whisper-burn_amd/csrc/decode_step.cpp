@@ -327,8 +327,10 @@ static int enqueue_logits_tail(StepCtx& c, bool timed, bool merge_prepares, int*
   const int d = c.d, V = c.V, S = c.S, n = c.n, k = call.k;
   const StepLayout& L = s->lay;
   const BeamStepIO* bio = call.bio;
-  int32_t* out_id_dev = bio ? bio->topk_id : reinterpret_cast<int32_t*>(s->host_block_dev + (size_t)L.total * 4);
-  float* out_lp_dev = bio ? bio->topk_lp : reinterpret_cast<float*>(s->host_block_dev + (size_t)L.total * 4 + (size_t)S * TOPK_MAX * 4);
+  const SampleStepIO* sio = call.sio;
+  int32_t* out_id_dev = bio ? bio->topk_id : sio ? sio->topk_id : reinterpret_cast<int32_t*>(s->host_block_dev + (size_t)L.total * 4);
+  float* out_lp_dev = bio ? bio->topk_lp : sio ? sio->topk_lp
+                          : reinterpret_cast<float*>(s->host_block_dev + (size_t)L.total * 4 + (size_t)S * TOPK_MAX * 4);
   const float* pend = s->P2.as<float>(); const float* pbias = m->dec[c.NL - 1].mlp2.b;   // what the last layer left pending
   if (!p.fuse_ln) c.resolve(pend, p.k2, pbias, m->ln_dec);
   ScopedTimer tm_logits(st, 6);
@@ -361,6 +363,12 @@ static int enqueue_logits_tail(StepCtx& c, bool timed, bool merge_prepares, int*
                           s->row_stats.as<float>(), L, gctl, s->gtok.as<int>(), s->Lmax, call.eot, nx);
   }
   if (bio) { prof_tag(KC_BEAM_UPDATE, 8.0 * n * k); launch_dec_beam_update(st, bio->upd); }
+  if (sio) {   // the draw reads the row's logits (and the mask) once
+    SampleChainArgs u = sio->upd;
+    u.use_mask = call.use_mask;
+    prof_tag(KC_SAMPLE_UPDATE, (call.use_mask ? 8.0 : 4.0) * (double)n * V);
+    launch_dec_sample_update(st, u, n);
+  }
   if (timed && tm_logits.on) {
     WB_HIP(hipStreamSynchronize(st));
     tm_logits.collect();
@@ -382,8 +390,8 @@ static int enqueue_step(wb_session* s, const StepPlan& p, const StepCall& call, 
   // chained small-batch steps: the previous step's merge kernel already prepared this one (the chain's
   // first step is prepared by session_greedy_chain)
   const bool merge_prepares = call.chained && p.fuse_ln;
-  // (device-chained beam search: the bookkeeping launch behind the previous step prepared this one)
-  if (!merge_prepares && !bio) {
+  // (device-chained beam search / sampling: the bookkeeping launch behind the previous step prepared this one)
+  if (!merge_prepares && !bio && !call.sio) {
     prof_tag(KC_PREPARE, 8.0 * c.n * c.d);
     launch_dec_prepare(c.st, hst, s->state.as<int>(), s->lay, c.n, c.tabs, s->Lmax, s->m->tok_emb, s->m->dec_pos, c.d, c.xb[0], gctl);
   }
@@ -399,7 +407,7 @@ int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call) {
   if (!plan.use_graph) {
     for (int i = 0; i < reps; i++) {
       WB_TRY(enqueue_step(s, plan, call, true));
-      if (call.chained || call.bio) s->prof_step_off++;
+      if (call.chained || call.bio || call.sio) s->prof_step_off++;
     }
     return WB_OK;
   }
@@ -425,8 +433,9 @@ int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call) {
   // first step's position via the control block layout: session_beam_chain drops the graphs when those change)
   // (the rest of the plan follows from n_launch, fuse_ln and what the signature above carries: the model, S, W, max_beams,
   // n_chunks, maxC -- and the process's switches)
-  const uint64_t key = ((uint64_t)reps << 48) | ((uint64_t)plan.n_launch << 32) | ((uint64_t)call.k << 8) | (call.bio ? 8u : 0u) |
-                       (call.chained ? 4u : 0u) | ((uint64_t)call.use_mask << 1) | (plan.fuse_ln ? 1u : 0u);
+  // (a sampling-chain graph bakes in its control block and max_depth: session_sample_chain drops ITS graphs when those change)
+  const uint64_t key = ((uint64_t)reps << 48) | ((uint64_t)plan.n_launch << 32) | ((uint64_t)call.k << 8) | (call.sio ? GRAPH_KEY_SAMPLE : 0u) |
+                       (call.bio ? 8u : 0u) | (call.chained ? 4u : 0u) | ((uint64_t)call.use_mask << 1) | (plan.fuse_ln ? 1u : 0u);
   auto it = s->graphs.find(key);
   if (it == s->graphs.end()) {
     hipGraph_t g = nullptr;
@@ -442,6 +451,7 @@ int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call) {
     WB_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
     it = s->graphs.emplace(key, ge).first;
+    s->n_captures++;
   }
   WB_HIP(hipGraphLaunch(it->second, st));
   return WB_OK;

@@ -20,6 +20,8 @@ enum KernelClass {
   KC_ALIGN_STATS, KC_ALIGN_ACCUM, KC_ALIGN_DTW,
   // token scoring (score.hip): one launch each per scoring call
   KC_SCORE_LOGITS, KC_SCORE_MERGE,
+  // temperature sampling (sample.hip): the draw + bookkeeping launch behind a sampling step's logits tail
+  KC_SAMPLE_UPDATE,
   KC_COUNT
 };
 void prof_tag(int cls, double algo_bytes);

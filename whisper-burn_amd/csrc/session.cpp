@@ -82,6 +82,7 @@ int session_create(wb_model* m, int n_windows, int max_beams, int padding, wb_se
   s->prev_len.clear(); s->prev_win.clear(); s->prev_n = 0; s->step = 0;
   s->has_mask = false; s->decode_ready = false; s->last_had_logits = 0; s->last_use_mask = 0;
   s->sample_rate = 16000.0;          // per-use state: a pooled session must not remember its previous caller
+  s->smp_best_of = 0; s->smp_depth = 0; s->smp_len.clear(); s->smp_tokens.clear();
   *out = s;
   return WB_OK;
 }

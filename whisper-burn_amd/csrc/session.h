@@ -41,6 +41,11 @@ struct wb_session {
   int n_tiles_v = 0, ct_v = 128;
   int ks_qkv = 1, ksl_qkv = 0, ks_o = 1, ksl_o = 0, ks_1 = 1, ksl_1 = 0, ks_2 = 1, ksl_2 = 0, ks_v = 1, ksl_v = 0;
   wb::DevMem bc_ctl, bc_topk;   // device-chained beam search (decode.h: BeamChainArgs): control block, top-k rows of the step
+  wb::DevMem sc_ctl, sc_topk;   // device-chained sampling (decode.h: SampleChainArgs): control block, the steps' top-1 rows
+  uint64_t sample_sig = 0;      // what the captured sampling steps bake in (session_sample_chain)
+  // every sample of the last sampling call (wb_session_last_samples): generated tokens [W][best_of][depth], their counts
+  // [W][best_of] (-1: the window was not active)
+  std::vector<int32_t> smp_tokens, smp_len; int smp_best_of = 0, smp_depth = 0;
   std::vector<int> prev_len, prev_win;
   int prev_n = 0, step = 0;
   bool has_mask = false, decode_ready = false;
@@ -56,6 +61,7 @@ struct wb_session {
   bool enc_guard_pending = false;   // the encode pass was enqueued with a deferred check (session_enc_guard_resolve)
   wb::MelBatch enc_mb;              // ... its input, kept so the pass can be repeated on the exact-f32 kernel
   std::unordered_map<uint64_t, hipGraphExec_t> graphs;   // captured decode steps, keyed by launch shape
+  int64_t n_captures = 0;                                // step graphs captured over the session's life (wb_session_graph_captures)
   uint64_t buf_sig = 0;                                  // signature of the buffers the graphs were captured with
   uint64_t beam_sig = 0;                                 // ... and of the constants of the last device-chained beam search
   void clear_graphs();
@@ -96,6 +102,12 @@ int session_reserve(wb_session* s, int max_len);
 // served (the caller runs the host-driven search)
 int session_beam_chain(wb_session* s, const int32_t* prompt, int prompt_len, int beam_size, int eot, int max_depth,
                        int mask_until_len, int32_t* out_tokens, int32_t row_stride, int32_t* out_lens, bool* handled);
+// temperature sampling with the draw and the bookkeeping on the device (sample_chain.cpp); active / stream_ids / out_sum /
+// out_best may be null
+struct SampleCall { float temperature; int best_of; uint64_t seed; int attempt; };
+int session_sample_chain(wb_session* s, const int32_t* prompt, int prompt_len, const SampleCall& sp, const uint8_t* active,
+                         const int32_t* stream_ids, int eot, int max_depth, int mask_until_len, int32_t* out_tokens,
+                         int32_t row_stride, int32_t* out_lens, double* out_sum, int32_t* out_best);
 int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_depth, int mask_until_len, int prompt_len,
                          int32_t* out_tokens, int32_t row_stride, int32_t* out_lens);
 // wb_session_align (align.cpp); drop_last_rows non-null: drop_last per window instead of the scalar, and a row that leaves

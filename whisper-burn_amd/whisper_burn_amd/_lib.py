@@ -32,6 +32,19 @@ class WbDecodeParams(C.Structure):
         "tok_end_of_text")]
 
 
+class WbSampleParams(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("best_of", C.c_int32), ("seed", C.c_uint64), ("attempt", C.c_int32)]
+
+
+class WbFallbackParams(C.Structure):
+    _fields_ = [("temperatures", C.c_float * 8), ("n_temperatures", C.c_int32), ("best_of", C.c_int32),
+                ("logprob_threshold", C.c_float), ("no_speech_threshold", C.c_float),
+                ("compression_ratio_threshold", C.c_float), ("seed", C.c_uint64), ("tok_no_speech", C.c_int32)]
+
+
+# wb_ratio_fn (include/whisper_hip.h)
+RATIO_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, c_int32_p, C.c_int32)
+
 # wb_step_fn (include/whisper_hip.h)
 STEP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_int32_p, c_int32_p, c_int32_p, C.c_int, C.c_int, C.c_int,
                       c_int32_p, c_float_p)
@@ -139,6 +152,24 @@ SIGNATURES = {
     "wb_logprob_gather": (C.c_int, [C.c_int, c_float_p, C.c_int32, C.c_int32, c_float_p, C.c_int32, c_float_p, c_uint8_p,
                                     c_int32_p, c_int32_p, c_int32_p, C.c_int32, C.c_int32, c_float_p, c_float_p,
                                     c_float_p]),
+    "wb_sample_params_default": (None, [C.POINTER(WbSampleParams)]),
+    "wb_session_rewind": (C.c_int, [C.c_void_p]),
+    "wb_session_graph_count": (C.c_int, [C.c_void_p]),
+    "wb_session_graph_captures": (C.c_int64, [C.c_void_p]),
+    "wb_session_decode_sample": (C.c_int, [C.c_void_p, C.POINTER(WbDecodeParams), C.POINTER(WbSampleParams), c_int32_p,
+                                           C.c_int32, c_uint8_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_double_p,
+                                           c_int32_p]),
+    "wb_session_last_samples": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_int32_p]),
+    "wb_fallback_params_default": (None, [C.POINTER(WbFallbackParams)]),
+    "wb_fallback_decide": (C.c_int, [C.POINTER(WbFallbackParams), C.c_float, C.c_float, C.c_float]),
+    "wb_waveform_to_tokens_fallback": (C.c_int, [C.c_void_p, c_float_p, C.c_int64, C.c_int, C.POINTER(WbDecodeParams),
+                                                 c_uint8_p, C.c_int, C.c_int, c_int32_p, C.c_int32, c_int32_p,
+                                                 c_int32_p, C.c_int64, c_int64_p, C.POINTER(WbFallbackParams), C.c_void_p,
+                                                 C.c_void_p, c_float_p, c_int32_p, c_float_p, c_float_p, c_float_p,
+                                                 c_int32_p]),
+    "wb_sample_rows": (C.c_int, [C.c_int, c_float_p, C.c_int32, C.c_int32, C.c_int32, c_float_p, c_uint8_p, c_float_p,
+                                 C.c_float, C.c_uint64, C.c_int32, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_float_p,
+                                 c_int32_p]),
     "wb_first_repetition_end": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_repetition_period": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_find_repeated_tokens_index": (C.c_int, [c_int32_p, C.c_int64, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),

@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import WbDecodeParams, WbDims, WbError, check
+from ._lib import WbDecodeParams, WbDims, WbError, WbFallbackParams, WbSampleParams, check
 from .tokens import SpecialTokens
 
 WB_F32, WB_BF16 = 0, 1
@@ -97,6 +97,135 @@ def logprob_gather(h, E, target=None, mask=None, row_masked=None, probes=None, v
                                         _ip(pid) if pr is not None else None, n_probe, v_splits, _fp(lp), _fp(lse),
                                         _fp(plp)))
     return lp, lse, plp[:n_probe]
+
+
+def sample_rows(logits, row_stats, temperature: float, seed: int, attempt, stream, position, eot: int, V: Optional[int] = None,
+                mask=None, row_masked=None, device: int = 0):
+    """The Gumbel-max draw alone (wb_sample_rows, a test hook): logits [R, ld] of which the first V columns are the row,
+    row_stats [R, 2] = (row maximum, log-sum-exp) under the row's mask -> (token [R], logprob [R], error word)."""
+    x = _f32(logits)
+    R, ld = x.shape
+    V = ld if V is None else V
+    stt = _f32(row_stats)
+    sid, pos = _i32(stream), _i32(position)
+    assert stt.shape == (R, 2) and sid.shape == (R,) and pos.shape == (R,)
+    mk = _f32(mask) if mask is not None else None
+    rm = np.ascontiguousarray(row_masked, dtype=np.uint8) if row_masked is not None else None
+    tok = np.full(R, -1, dtype=np.int32)
+    lp = np.full(R, np.nan, dtype=np.float32)
+    err = np.full(1, -1, dtype=np.int32)
+    check(_lib.load().wb_sample_rows(device, _fp(x), R, ld, V, _fp(mk) if mk is not None else None, _u8p(rm), _fp(stt),
+                                     float(temperature), int(seed), int(attempt), _ip(sid), _ip(pos), int(eot), _ip(tok),
+                                     _fp(lp), _ip(err)))
+    return tok, lp, int(err[0])
+
+
+def SampleParams(temperature: float = 1.0, best_of: int = 5, seed: int = 0, attempt: int = 0) -> WbSampleParams:
+    """wb_sample_params: one sampled decode at `temperature`, best of `best_of` per window."""
+    p = WbSampleParams()
+    _lib.load().wb_sample_params_default(C.byref(p))
+    p.temperature, p.best_of, p.seed, p.attempt = temperature, best_of, seed, attempt
+    return p
+
+
+def FallbackParams(temperatures=None, best_of: Optional[int] = None, logprob_threshold: Optional[float] = -1.0,
+                   no_speech_threshold: Optional[float] = 0.6, compression_ratio_threshold: Optional[float] = 2.4,
+                   seed: int = 0, tok_no_speech: int = -1) -> WbFallbackParams:
+    """wb_fallback_params with Whisper's defaults; None for a threshold switches its rule off."""
+    p = WbFallbackParams()
+    _lib.load().wb_fallback_params_default(C.byref(p))
+    if temperatures is not None:
+        ts = [float(t) for t in temperatures]
+        if not 1 <= len(ts) <= 8:
+            raise ValueError("fallback: 1 .. 8 temperatures")
+        for i in range(8):
+            p.temperatures[i] = ts[i] if i < len(ts) else 0.0
+        p.n_temperatures = len(ts)
+    if best_of is not None:
+        p.best_of = best_of
+    nan = float("nan")
+    p.logprob_threshold = nan if logprob_threshold is None else logprob_threshold
+    p.no_speech_threshold = nan if no_speech_threshold is None else no_speech_threshold
+    p.compression_ratio_threshold = nan if compression_ratio_threshold is None else compression_ratio_threshold
+    p.seed, p.tok_no_speech = seed, tok_no_speech
+    return p
+
+
+FALLBACK_ACCEPT, FALLBACK_RETRY, FALLBACK_NO_SPEECH = 0, 1, 2
+
+
+def fallback_decide(params: WbFallbackParams, avg_logprob: float, no_speech_prob: float, ratio: float) -> int:
+    """Whisper's accept (0) / retry (1) / no speech (2) decision for one window (wb_fallback_decide, host only)."""
+    return int(_lib.load().wb_fallback_decide(C.byref(params), float(avg_logprob), float(no_speech_prob), float(ratio)))
+
+
+def compression_ratio(text: str) -> float:
+    """Whisper's compression ratio: len(utf8) / len(zlib.compress(utf8))."""
+    import zlib
+    b = text.encode("utf-8")
+    return len(b) / len(zlib.compress(b))
+
+
+def ratio_from_tokenizer(bpe):
+    """The `ratio` callback of waveform_to_tokens_fallback from a tokenizer adapter (`decode(tokens, skip_special) -> str`)."""
+    def ratio(tokens: List[int]) -> float:
+        return compression_ratio(bpe.decode(list(tokens), True))
+    return ratio
+
+
+def waveform_to_tokens_fallback(whisper: "Whisper", st: SpecialTokens, waveform, sample_rate: int = 16000,
+                                beam_size: int = 5, max_depth: int = 100, win_begin: int = 0, win_end: int = -1,
+                                params: Optional[WbDecodeParams] = None, fallback: Optional[WbFallbackParams] = None,
+                                ratio=None):
+    """waveform_to_tokens with Whisper's decode fallback (wb_waveform_to_tokens_fallback): a window whose decode fails
+    the thresholds is decoded again by sampling at the next temperature, on the same session; silent windows are left out
+    of the stitched stream.  ratio: callable(list of generated token ids) -> compression ratio, or None (rule off).
+
+    Returns a dict: tokens (stitched), win_tokens, and per local window temperature, status (0 accepted, 1 failed every
+    temperature, 2 no speech), avg_logprob, no_speech_prob, ratio, attempts."""
+    lib = _lib.load()
+    wav = _f32(waveform).reshape(-1)
+    p = params or decode_params(st, beam_size, max_depth)
+    fp = fallback or FallbackParams(tok_no_speech=st.no_speech)
+    wlen = max_waveform_samples(whisper.max_mel_frames() - p.padding)
+    starts, _ = window_extents(len(wav), sample_rate, wlen, p.overlap_seconds)
+    if win_end < 0:
+        win_end = len(starts)
+    n_local = max(0, win_end - win_begin)
+    nw = max(n_local, 1)
+    stride = 4 + p.max_depth + 4
+    win_tokens = np.zeros((nw, stride), dtype=np.int32)
+    win_lens = np.zeros(nw, dtype=np.int32)
+    cap = nw * stride
+    stitched = np.zeros(cap, dtype=np.int32)
+    n_st = C.c_int64(0)
+    temp = np.full(nw, np.nan, dtype=np.float32)
+    status = np.full(nw, -1, dtype=np.int32)
+    avg = np.full(nw, np.nan, dtype=np.float32)
+    nsp = np.full(nw, np.nan, dtype=np.float32)
+    rat = np.full(nw, np.nan, dtype=np.float32)
+    att = np.zeros(nw, dtype=np.int32)
+    mask = special_mask_bytes(whisper, st.is_special)
+    failure = []
+
+    def _ratio(_user, toks, n):
+        try:
+            return float(ratio([int(toks[i]) for i in range(n)]))
+        except Exception as e:  # nothing unwinds across the C boundary
+            failure.append(e)
+            return float("nan")
+    cb = _lib.RATIO_FN(_ratio) if ratio is not None else None
+    check(lib.wb_waveform_to_tokens_fallback(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p),
+                                             mask.ctypes.data_as(_lib.c_uint8_p), win_begin, win_end, _ip(win_tokens), stride,
+                                             _ip(win_lens), _ip(stitched), cap, C.byref(n_st), C.byref(fp),
+                                             C.cast(cb, C.c_void_p) if cb is not None else None, None, _fp(temp),
+                                             _ip(status), _fp(avg), _fp(nsp), _fp(rat), _ip(att)))
+    if failure:
+        raise failure[0]
+    n = n_local
+    return dict(tokens=stitched[:n_st.value].tolist(), win_tokens=[win_tokens[i, :win_lens[i]].tolist() for i in range(n)],
+                temperature=temp[:n].copy(), status=status[:n].copy(), avg_logprob=avg[:n].copy(),
+                no_speech_prob=nsp[:n].copy(), ratio=rat[:n].copy(), attempts=att[:n].copy())
 
 
 def special_mask_bytes(whisper: "Whisper", is_special) -> np.ndarray:
@@ -668,6 +797,50 @@ class Session:
         lens = np.zeros(self.n_windows, dtype=np.int32)
         check(_lib.load().wb_session_decode(self._h, C.byref(params), _ip(toks), stride, _ip(lens)))
         return [toks[i, :lens[i]].tolist() for i in range(self.n_windows)]
+
+    def rewind(self) -> None:
+        """Back to step 0 over the same encoded windows (wb_session_rewind): another decode costs decode steps only."""
+        check(_lib.load().wb_session_rewind(self._h))
+
+    def graph_count(self) -> int:
+        """Captured step graphs the session holds (debug)."""
+        return int(_lib.load().wb_session_graph_count(self._h))
+
+    def graph_captures(self) -> int:
+        """Step graphs captured over the session's life (debug): unchanged by a call that only replays."""
+        return int(_lib.load().wb_session_graph_captures(self._h))
+
+    def decode_sample(self, params: WbDecodeParams, sample: WbSampleParams, prompt=None, active=None, stream_ids=None,
+                      out_tokens: Optional[np.ndarray] = None, out_lens: Optional[np.ndarray] = None):
+        """best_of sampled sequences per window at sample.temperature (wb_session_decode_sample), on a fresh or rewound
+        session.  prompt: default the four-token prompt of `params`; active [W]: windows to decode (default all);
+        stream_ids [W]: base stream of each window (default w * best_of); out_tokens / out_lens: arrays to write into
+        (rows of inactive windows stay as they are).  Returns (rows, sum_logprob [W, best_of] f64, best [W])."""
+        W, bo = self.n_windows, int(sample.best_of)
+        pr = _i32([params.tok_start_of_transcript, params.tok_language, params.tok_transcribe, params.tok_no_timestamps]
+                  if prompt is None else list(prompt))
+        stride = len(pr) + params.max_depth + 4
+        toks = out_tokens if out_tokens is not None else np.zeros((W, stride), dtype=np.int32)
+        lens = out_lens if out_lens is not None else np.zeros(W, dtype=np.int32)
+        assert toks.dtype == np.int32 and toks.flags.c_contiguous and toks.shape[0] == W and lens.dtype == np.int32
+        act = np.ascontiguousarray(active, dtype=np.uint8) if active is not None else None
+        sid = _i32(stream_ids) if stream_ids is not None else None
+        sums = np.full((W, max(bo, 1)), np.nan, dtype=np.float64)
+        best = np.full(W, -1, dtype=np.int32)
+        check(_lib.load().wb_session_decode_sample(self._h, C.byref(params), C.byref(sample), _ip(pr), len(pr), _u8p(act),
+                                                   _ip(sid) if sid is not None else None, _ip(toks), toks.shape[1], _ip(lens),
+                                                   sums.ctypes.data_as(_lib.c_double_p), _ip(best)))
+        return [toks[i, :lens[i]].tolist() for i in range(W)], sums, best
+
+    def last_samples(self, best_of: int, max_depth: int) -> List[List[Optional[List[int]]]]:
+        """Every sample of the last decode_sample (wb_session_last_samples): [W][best_of] lists of generated tokens (without
+        the prompt); None for the windows that were not active."""
+        W = self.n_windows
+        toks = np.zeros((W * best_of, max(max_depth, 1)), dtype=np.int32)
+        lens = np.zeros(W * best_of, dtype=np.int32)
+        check(_lib.load().wb_session_last_samples(self._h, _ip(toks), toks.shape[1], _ip(lens)))
+        return [[toks[w * best_of + j, :lens[w * best_of + j]].tolist() if lens[w * best_of + j] >= 0 else None
+                 for j in range(best_of)] for w in range(W)]
 
     def align(self, tokens, lens=None, heads=None, n_prefix: int = 4, drop_last: int = 1, filter_width: int = 7,
               return_matrix: bool = False):

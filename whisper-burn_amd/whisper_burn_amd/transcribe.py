@@ -21,6 +21,13 @@ with `--token-times` the audio is decoded once per option: each is one library c
 `<lang>` = `auto` detects the language from the first windows of the audio (wb_waveform_detect_language over the
 language tokens the tokenizer knows) and prints it before decoding; a tokenizer without language tokens is an error.
 
+`--fallback` switches Whisper's decode fallback on (wb_waveform_to_tokens_fallback): a window whose decode fails the
+thresholds is decoded again by sampling at the next temperature, and windows without speech are left out of the transcript.
+Optional with it: `--temperatures 0,0.2,...` (the first must be 0), `--best-of N`, `--seed N`, `--logprob-threshold X`,
+`--no-speech-threshold X`, `--compression-ratio-threshold X` (`none` switches a rule off).  With `--scores PATH` the file then
+holds the per-window lines only, and each gains `temperature` and `status` (0 accepted, 1 failed every temperature, 2 no
+speech).
+
 One addition: with `WHISPER_HIP_RESAMPLE=1` in the environment a mono WAV of another sample rate (the bundled
 22 050 Hz audio.wav, which the reference sends through `sox`, README.md:69-74) is resampled to 16 kHz on the GPU
 (wb_resample_dev) instead of being rejected.
@@ -44,9 +51,27 @@ def main(argv=None) -> int:
     scores_file = None
     extra = argv[5:]
     usage = (f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference] "
-             f"[--token-times PATH] [--scores PATH]")
+             f"[--token-times PATH] [--scores PATH] [--fallback [--temperatures T0,T1,..] [--best-of N] [--seed N] "
+             f"[--logprob-threshold X] [--no-speech-threshold X] [--compression-ratio-threshold X]]")
+    fallback = False
+    fb = {}                                     # keyword arguments of FallbackParams given on the command line
+    fb_opts = {"--temperatures": ("temperatures", lambda v: [float(t) for t in v.split(",")]), "--best-of": ("best_of", int),
+               "--seed": ("seed", int), "--logprob-threshold": ("logprob_threshold", float),
+               "--no-speech-threshold": ("no_speech_threshold", float),
+               "--compression-ratio-threshold": ("compression_ratio_threshold", float)}
     while extra:                                # (other trailing arguments are ignored, as before)
-        if extra[0] in ("--frontend", "--token-times", "--scores"):
+        if extra[0] == "--fallback":
+            fallback = True
+            extra = extra[1:]
+        elif extra[0] in fb_opts:
+            key, conv = fb_opts[extra[0]]
+            try:
+                fb[key] = None if key.endswith("threshold") and extra[1] == "none" else conv(extra[1])
+            except (IndexError, ValueError):
+                print(usage, file=sys.stderr)
+                return 1
+            extra = extra[2:]
+        elif extra[0] in ("--frontend", "--token-times", "--scores"):
             if len(extra) < 2 or (extra[0] == "--frontend" and extra[1] not in ("fft", "reference")):
                 print(usage, file=sys.stderr)
                 return 1
@@ -59,6 +84,12 @@ def main(argv=None) -> int:
             extra = extra[2:]
         else:
             extra = extra[1:]
+    if fb and not fallback:
+        print("The fallback options (--temperatures, --best-of, --seed, --*-threshold) need --fallback\n" + usage, file=sys.stderr)
+        return 1
+    if fallback and times_file is not None:
+        print("--token-times is not available together with --fallback\n" + usage, file=sys.stderr)
+        return 1
     if lang != "auto" and lang not in LANGUAGES:
         print(f"Invalid language abbreviation: {lang}", file=sys.stderr)
         return 1
@@ -121,8 +152,16 @@ def main(argv=None) -> int:
 
     token_times = None
     scores = None
+    fb_result = None
     try:
-        if times_file is None and scores_file is None:
+        if fallback:
+            st = bpe.special_tokens(lang)
+            fb_result = wb.waveform_to_tokens_fallback(whisper, st, waveform, sample_rate,
+                                                       fallback=wb.FallbackParams(tok_no_speech=st.no_speech, **fb),
+                                                       ratio=wb.ratio_from_tokenizer(bpe))
+            _tokens = fb_result["tokens"]
+            text = bpe.decode(_tokens, True)
+        elif times_file is None and scores_file is None:
             text, _tokens = wb.waveform_to_text(whisper, Bpe(), lang, waveform, sample_rate)
         else:
             st = bpe.special_tokens(lang)
@@ -161,12 +200,20 @@ def main(argv=None) -> int:
             return float(x) if math.isfinite(float(x)) else None         # (NaN: no value; -inf cannot be JSON either)
         try:
             with open(scores_file, "w") as fh:
-                for tok, lp in zip(scores["tokens"], scores["logprobs"]):
-                    if st.is_special[tok]:
-                        continue
-                    fh.write(json.dumps({"id": int(tok), "text": bpe.decode([tok], True), "logprob": num(lp)}) + "\n")
-                for w, (a, n) in enumerate(zip(scores["avg_logprob"], scores["no_speech_prob"])):
-                    fh.write(json.dumps({"window": w, "avg_logprob": num(a), "no_speech_prob": num(n)}) + "\n")
+                if fb_result is not None:
+                    # (the fallback call returns no per-token log-probs: the file holds the per-window lines only)
+                    r = fb_result
+                    for w in range(len(r["status"])):
+                        fh.write(json.dumps({"window": w, "avg_logprob": num(r["avg_logprob"][w]),
+                                             "no_speech_prob": num(r["no_speech_prob"][w]),
+                                             "temperature": num(r["temperature"][w]), "status": int(r["status"][w])}) + "\n")
+                else:
+                    for tok, lp in zip(scores["tokens"], scores["logprobs"]):
+                        if st.is_special[tok]:
+                            continue
+                        fh.write(json.dumps({"id": int(tok), "text": bpe.decode([tok], True), "logprob": num(lp)}) + "\n")
+                    for w, (a, n) in enumerate(zip(scores["avg_logprob"], scores["no_speech_prob"])):
+                        fh.write(json.dumps({"window": w, "avg_logprob": num(a), "no_speech_prob": num(n)}) + "\n")
         except OSError as e:
             print(f"Error writing scores file: {e}", file=sys.stderr)
             return 1
