@@ -489,6 +489,11 @@ int wb_session_rewind(wb_session* s);
 int wb_session_graph_count(const wb_session* s);
 /* Debug / tests: step graphs captured over the session's life (a replayed graph does not count). */
 int64_t wb_session_graph_captures(const wb_session* s);
+/* Debug / tests: the LDS-resident operand geometry of the persistent greedy kernel's instance that serves (n_state, live rows,
+ * longest encoder context in keys) -- out5 = {resident float4 slots per thread, resident QKV weight rounds, resident Wo rows
+ * of the self-attention role, resident V tiles and resident Wo rows of the cross-attention role}.  Needs no device.
+ * WB_ERR_SHAPE if no instance serves the shape. */
+int wb_persist_resident_geometry(int32_t n_state, int32_t n_rows, int32_t max_keys, int32_t* out5);
 /* best_of independent sampled sequences per window from `prompt`, on a fresh or rewound session; the draw and the row
  * bookkeeping run on the device, chunks of steps replay as one graph (the same graph for every temperature and seed).
  * active [W] (NULL = all): windows with active[w] == 0 are not decoded and nothing of theirs is written.

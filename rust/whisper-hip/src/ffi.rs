@@ -156,6 +156,7 @@ extern "C" {
     pub fn wb_session_rewind(s: *mut wb_session) -> c_int;
     pub fn wb_session_graph_count(s: *const wb_session) -> c_int;
     pub fn wb_session_graph_captures(s: *const wb_session) -> i64;
+    pub fn wb_persist_resident_geometry(n_state: i32, n_rows: i32, max_keys: i32, out5: *mut i32) -> c_int;
     pub fn wb_session_last_samples(s: *mut wb_session, tokens: *mut i32, row_stride: i32, lens: *mut i32) -> c_int;
     pub fn wb_sample_rows(device: c_int, logits: *const c_float, R: i32, ld: i32, V: i32, mask: *const c_float,
                           row_masked: *const u8, row_stats: *const c_float, temperature: c_float, seed: u64, attempt: i32,

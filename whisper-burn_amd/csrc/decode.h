@@ -320,11 +320,13 @@ struct PersistArgs {
 int ps_ctl_ints(int S, int n_layer);
 bool dec_persist_supported(int d, int n_rows, int max_keys);
 int dec_persist_resident_slots(int d, int n_rows, int max_keys);   // resident float4 slots per thread; 0: nothing useful fits
+bool dec_persist_resident_geometry(int d, int n_rows, int max_keys, int out[5]);   // {RS, NRND, NWO_A, NVT, NWO_X} of that instance
 // grid: blocks of 512 threads that are co-resident on this device for (d, n_rows) -- 0 if the kernel cannot run
 int dec_persist_max_grid(int device, int d, int n_rows, int max_keys);
 int launch_dec_persist(hipStream_t st, const PersistArgs& a, int grid);
-// seeds the granule copy of the first step's x rows: tag = tag_base + 1 (what the first self-attention blocks expect)
-void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned tag);
+// seeds the granule copy of the first step's x rows: tag = tag_base + 1 (what the first self-attention blocks expect), and
+// the control block's stop word (ctl: the HX_* words, zeroed on the stream in front of this): HX_STOP = INT_MAX, the decode goes on
+void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned tag, int* ctl);
 
 #if defined(HIPEMU) && !defined(HIPEMU_PROD_GEOMETRY)
 // (functional-model build: three tiles per pass, so that micro models run both rings -- one pass at n_audio_ctx = 400

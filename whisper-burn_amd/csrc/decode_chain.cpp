@@ -11,20 +11,31 @@ using namespace wb;
 
 namespace wb {
 
-// The whole chained greedy decode as ONE persistent launch (decode_persist.hip): every sublayer of every step runs in a
-// co-resident grid whose blocks hand their output planes to each other through arrival counters.  Enqueues the first
-// step's prepare kernel, the control block and the launch, then waits for the stream.  *steps_done = steps executed.
-//
-// *fell_back: the launch was refused (no cooperative launch on this device / partition, the grid not co-resident, a
-// second cooperative client) or a wait gave up before ANY step was committed -- the caller re-seeds the control block and
-// runs the graph-replayed chain of one launch per sublayer instead (it derives everything from gctl), and the session
-// stops trying the persistent kernel.  A wait that gives up after steps were committed stays an error.
-static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_until_len, const int32_t* forced, int n_forced,
-                                int* steps_done, bool* fell_back) {
-  *fell_back = false;
-  WB_REQUIRE(n_forced >= 0 && n_forced <= PS_MAX_FORCED, WB_ERR_ARG, "persistent decode: %d prompt steps", n_forced);
-  // test hook (tests/test_emu_functional.py, tests/test_gpu_switches.py): "launch" = behave as if the cooperative launch was refused
-  const char* inject = sw::persist_inject_fail();
+// Pinned host words of a greedy call (session.h: ps_pin): the control block's seed, then the words the host reads back.
+struct PsPin { size_t seed, err, gctl, tok, total, ctl_ints; };
+static PsPin ps_pin_layout(size_t ctl_ints, size_t tok_ints) {
+  PsPin p;
+  p.seed = 0; p.err = (ctl_ints + 3) & ~(size_t)3; p.gctl = p.err + 4; p.tok = p.gctl + ((ctl_ints + 3) & ~(size_t)3);
+  p.total = p.tok + tok_ints; p.ctl_ints = ctl_ints;
+  return p;
+}
+static int ps_pin_ensure(wb_session* s, size_t ints) {
+  if (s->ps_pin_ints >= ints) return WB_OK;
+  if (s->ps_pin_busy) { WB_HIP(hipStreamSynchronize(s->st)); s->ps_pin_busy = false; }
+  if (s->ps_pin) { (void)hipHostFree(s->ps_pin); s->ps_pin = nullptr; s->ps_pin_ints = 0; }
+  WB_HIP(hipHostMalloc((void**)&s->ps_pin, ints * 4, hipHostMallocDefault));
+  s->ps_pin_ints = ints;
+  return WB_OK;
+}
+
+// The launch setup of the persistent kernel: the per-layer argument blocks -- exactly what enqueue_step hands the fused
+// sublayer kernels -- and one step's roles dealt to the blocks, on the device (ps_layers, ps_roles).  All of it is a function
+// of the model (and its LayerNorm variant), the session's buffers, W, the grid, the window geometry and the resident switch
+// (what varies from call to call travels by value in PersistArgs), so a pooled session in a transcription loop builds and
+// uploads it once: it is kept under a key that names everything it was built from.  WHISPER_HIP_PERSIST_SETUP=0: built and
+// uploaded on every call (A/B runs); "log": one line per launch on stderr ("0log": both).  *built: this call built it (and
+// waited for the upload: the staging is on the stack).
+static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
   wb_model* m = s->m;
   const wb_dims& D = m->dims;
   const int d = D.n_text_state, H = D.n_text_head, NL = D.n_text_layer, V = D.n_vocab, S = s->S, W = s->W;
@@ -34,21 +45,22 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   const int n_tiles = (V + 127) / 128;
   const size_t pool = (size_t)s->Lmax * S;
   const int ldkv = 2 * d;
-  // ---- the hand-off buffers: residual streams and partial planes as {tag, value} granules (zero-filled once: tag 0 is
-  // never used; the tags of a launch live above launch_count << 16, so leftovers of earlier decodes never match)
-  WB_REQUIRE(NB <= 32 && H <= 8, WB_ERR_SHAPE, "persistent decode: more planes than its folds hold");
-  WB_TRY(s->ps_gx.ensure_zeroed(((size_t)2 * S + 8) * d * 8, st));
-  WB_TRY(s->ps_gpa.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
-  WB_TRY(s->ps_gpc.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
-  WB_TRY(s->ps_gp2.ensure_zeroed(((size_t)NB * S + 8) * d * 8, st));
-  WB_TRY(s->ps_gxn.ensure_zeroed(((size_t)S + 8) * d * 8, st));
-  if (((s->ps_launches + 1) & 0xffffu) == 0) {     // the 16-bit launch count wraps: forget every old tag
-    for (DevMem* b : {&s->ps_gx, &s->ps_gpa, &s->ps_gpc, &s->ps_gp2, &s->ps_gxn}) WB_HIP(hipMemsetAsync(b->p, 0, b->bytes, st));
-    s->ps_launches++;
-  }
-  const unsigned tag_base = ((++s->ps_launches) & 0xffffu) << 16;
+  const int n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;
+  const int n_layer_roles = NL * (2 * W * H + NB);
+  const int grid = std::max(1, std::min(s->ps_grid, n_layer_roles + n_tiles + 2 * W));
+  auto up = [](const void* p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); };
+  const std::vector<uint64_t> key = {
+      s->model_uid, (uint64_t)W, (uint64_t)S, (uint64_t)s->Lmax, (uint64_t)grid, (uint64_t)n_tiles, (uint64_t)n_pass,
+      (uint64_t)s->enc_rows, (uint64_t)res_on, (uint64_t)m->ln_eps_inside_sqrt, up(s->state.p), up(s->x.p), up(s->P2.p),
+      up(s->Pa.p), up(s->Pc.p), up(s->kc.p), up(s->vc.p), up(s->tabs.p), up(s->ckv.p), up(s->win_meta.p), up(s->ps_gx.p),
+      up(s->ps_gpa.p), up(s->ps_gpc.p), up(s->ps_gp2.p), up(s->ps_gxn.p)};
+  const char* sw_setup = sw::persist_setup();
+  const bool cache_on = !(sw_setup && sw_setup[0] == '0');
+  *built = !(cache_on && !s->ps_setup_key.empty() && s->ps_setup_key == key);
+  if (sw_setup && strstr(sw_setup, "log")) fprintf(stderr, "persist setup: %s\n", *built ? "built" : "reused");
+  if (!*built) return WB_OK;
+  s->ps_setup_key.clear();                           // void the cache key before the contents change
   char* gxb[2] = {static_cast<char*>(s->ps_gx.p), static_cast<char*>(s->ps_gx.p) + (size_t)S * d * 8};
-  // ---- per-layer arguments: exactly what enqueue_step hands the fused sublayer kernels ----
   std::vector<PsLayerArgs> la(NL);
   float* xb[2] = {s->x.as<float>(), s->x.as<float>() + (size_t)S * d};
   int xi = 0;
@@ -72,7 +84,7 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
     ca.ckv = s->ckv.as<float>() + (size_t)l * s->enc_rows * 2 * d; ca.ldkv = ldkv; ca.koff = 0;   // layer-major cached K|V
     ca.win_row0 = s->win_meta.as<int>(); ca.win_C = s->win_meta.as<int>() + W;
     ca.Wo = b.cout.w; ca.P = s->Pc.as<float>();
-    ca.n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;
+    ca.n_pass = n_pass;
     ca.g_x_in = gxb[xi]; ca.g_pend = s->ps_gpa.p; ca.g_x_out = gxb[xi ^ 1]; ca.g_P = s->ps_gpc.p;
     xi ^= 1;
     MlpFusedArgs& ma = la[l].mlp;
@@ -90,7 +102,6 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
     for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_CROSS, l, h, r});
     for (int j = 0; j < NB; j++) lr.push_back(PsRole{PSR_MLP, l, j, 0});
   }
-  const int grid = std::max(1, std::min(s->ps_grid, (int)lr.size() + n_tiles + 2 * W));
   std::vector<std::vector<PsRole>> deal(grid);
   for (size_t i = 0; i < lr.size(); i++) deal[i % grid].push_back(lr[i]);
   // logits: blocks that hold a first-layer attention role stay free of it -- they are the first to be needed in the next
@@ -136,46 +147,95 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   // list holds exactly ONE layer role, a self- or cross-attention one, runs that role every step -- the kernel keeps what
   // fits of the role's step-invariant operands in the LDS the roles leave free.  Blocks with several layer roles (a grid
   // smaller than the layer roles) would have to share the region: they run as before.
-  const char* res_sw = sw::persist_resident();
-  const bool res_on = !(res_sw && res_sw[0] == '0') && dec_persist_resident_slots(d, W, s->maxC) > 0;
   std::vector<int> res_role(grid, -1);              // per block: the index of its resident role
   int n_res = 0;
   if (res_on)
     for (int b = 0; b < grid; b++) {
-      int n_layer_roles = 0, at = -1;
+      int n_lr = 0, at = -1;
       for (int i = role_off[b]; i < role_off[b + 1]; i++)
-        if (roles[i].kind <= PSR_MLP) { n_layer_roles++; at = i; }
-      if (n_layer_roles == 1 && roles[at].kind != PSR_MLP) { res_role[b] = at; n_res++; }
+        if (roles[i].kind <= PSR_MLP) { n_lr++; at = i; }
+      if (n_lr == 1 && roles[at].kind != PSR_MLP) { res_role[b] = at; n_res++; }
     }
-  if (res_sw && !strcmp(res_sw, "log")) fprintf(stderr, "persist resident blocks: %d of %d\n", n_res, grid);
-  const int n_ctl = ps_ctl_ints(S, NL);
   WB_TRY(s->ps_layers.ensure(la.size() * sizeof(PsLayerArgs)));
   WB_TRY(s->ps_roles.ensure(roles.size() * sizeof(PsRole) + (role_off.size() + res_role.size()) * 4));
+  WB_HIP(hipMemcpyAsync(s->ps_layers.p, la.data(), la.size() * sizeof(PsLayerArgs), hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemcpyAsync(s->ps_roles.p, roles.data(), roles.size() * sizeof(PsRole), hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemcpyAsync(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole), role_off.data(), role_off.size() * 4,
+                        hipMemcpyHostToDevice, st));
+  WB_HIP(hipMemcpyAsync(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole) + role_off.size() * 4, res_role.data(),
+                        res_role.size() * 4, hipMemcpyHostToDevice, st));
+  WB_HIP(hipStreamSynchronize(st));            // (the staging vectors above are on the stack)
+  s->ps_pin_busy = false;
+  s->ps_roles_host.swap(roles);
+  s->ps_setup_grid = grid; s->ps_setup_n_lg = n_lg; s->ps_setup_n_res = n_res;
+  s->ps_setup_key = key;
+  return WB_OK;
+}
+
+// The whole chained greedy decode as ONE persistent launch (decode_persist.hip): every sublayer of every step runs in a
+// co-resident grid whose blocks hand their output planes to each other through arrival counters.  Enqueues the zeroing of the
+// polled words, the first step's prepare kernel and the launch behind whatever the stream still holds (the encoder: with the
+// launch setup cached nothing here waits for it), copies the words the host needs into pinned memory (ps_pin: error word,
+// control block, token rows) and waits for the stream ONCE.  *steps_done = steps executed.
+//
+// *fell_back: the launch was refused (no cooperative launch on this device / partition, the grid not co-resident, a
+// second cooperative client) or a wait gave up before ANY step was committed -- the caller re-seeds the control block and
+// runs the graph-replayed chain of one launch per sublayer instead (it derives everything from gctl), and the session
+// stops trying the persistent kernel.  A wait that gives up after steps were committed stays an error.
+static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_until_len, const int32_t* forced, int n_forced,
+                                const PsPin& pin, int* steps_done, bool* fell_back) {
+  *fell_back = false;
+  WB_REQUIRE(n_forced >= 0 && n_forced <= PS_MAX_FORCED, WB_ERR_ARG, "persistent decode: %d prompt steps", n_forced);
+  // test hook (tests/test_emu_functional.py, tests/test_gpu_switches.py): "launch" = behave as if the cooperative launch was refused
+  const char* inject = sw::persist_inject_fail();
+  wb_model* m = s->m;
+  const wb_dims& D = m->dims;
+  const int d = D.n_text_state, H = D.n_text_head, NL = D.n_text_layer, V = D.n_vocab, S = s->S, W = s->W;
+  const StepLayout& L = s->lay;
+  hipStream_t st = s->st;
+  const int NB = dec_mlp_fused_planes(d);
+  const int n_tiles = (V + 127) / 128;
+  // ---- the hand-off buffers: residual streams and partial planes as {tag, value} granules (zero-filled once: tag 0 is
+  // never used; the tags of a launch live above launch_count << 16, so leftovers of earlier decodes never match)
+  WB_REQUIRE(NB <= 32 && H <= 8, WB_ERR_SHAPE, "persistent decode: more planes than its folds hold");
+  WB_TRY(s->ps_gx.ensure_zeroed(((size_t)2 * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gpa.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gpc.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gp2.ensure_zeroed(((size_t)NB * S + 8) * d * 8, st));
+  WB_TRY(s->ps_gxn.ensure_zeroed(((size_t)S + 8) * d * 8, st));
+  if (((s->ps_launches + 1) & 0xffffu) == 0) {     // the 16-bit launch count wraps: forget every old tag
+    for (DevMem* b : {&s->ps_gx, &s->ps_gpa, &s->ps_gpc, &s->ps_gp2, &s->ps_gxn}) WB_HIP(hipMemsetAsync(b->p, 0, b->bytes, st));
+    s->ps_launches++;
+  }
+  const unsigned tag_base = ((++s->ps_launches) & 0xffffu) << 16;
+  char* gxb[2] = {static_cast<char*>(s->ps_gx.p), static_cast<char*>(s->ps_gx.p) + (size_t)S * d * 8};
+  // ---- per-layer arguments and the dealt roles: on the device, built only when what they were built from has changed ----
+  const char* res_sw = sw::persist_resident();
+  const bool res_on = !(res_sw && res_sw[0] == '0') && dec_persist_resident_slots(d, W, s->maxC) > 0;
+  bool built = false;
+  WB_TRY(ps_setup_ensure(s, res_on, &built));
+  const std::vector<PsRole>& roles = s->ps_roles_host;
+  const int grid = s->ps_setup_grid, n_res = s->ps_setup_n_res;
+  if (res_sw && !strcmp(res_sw, "log")) fprintf(stderr, "persist resident blocks: %d of %d\n", n_res, grid);
+  const int n_ctl = ps_ctl_ints(S, NL);
   WB_TRY(s->ps_ctl.ensure((size_t)n_ctl * 4));
   WB_TRY(s->ps_dead.ensure((size_t)S * 4));
   WB_TRY(s->ps_tstats.ensure((size_t)S * n_tiles * 2 * 4));
-  std::vector<int> ctl0(n_ctl, 0);
-  ctl0[HX_STOP] = INT_MAX;
-  WB_HIP(hipMemcpyAsync(s->ps_layers.p, la.data(), la.size() * sizeof(PsLayerArgs), hipMemcpyHostToDevice, st));
-  WB_HIP(hipMemcpyAsync(s->ps_roles.p, roles.data(), roles.size() * sizeof(PsRole), hipMemcpyHostToDevice, st));
-  WB_HIP(hipMemcpyAsync(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole) + role_off.size() * 4, res_role.data(),
-                        res_role.size() * 4, hipMemcpyHostToDevice, st));
-  WB_HIP(hipMemcpyAsync(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole), role_off.data(), role_off.size() * 4,
-                        hipMemcpyHostToDevice, st));
-  WB_HIP(hipMemcpyAsync(s->ps_ctl.p, ctl0.data(), (size_t)n_ctl * 4, hipMemcpyHostToDevice, st));
+  // the polled words start at zero; HX_STOP = INT_MAX is written by the seed kernel below
+  WB_HIP(hipMemsetAsync(s->ps_ctl.p, 0, (size_t)n_ctl * 4, st));
   WB_HIP(hipMemsetAsync(s->ps_dead.p, 0, (size_t)S * 4, st));
   PersistArgs a;
   a.layers = s->ps_layers.as<PsLayerArgs>(); a.roles = s->ps_roles.as<PsRole>(); a.n_roles = (int)roles.size();
   a.role_off = reinterpret_cast<const int*>(static_cast<char*>(s->ps_roles.p) + roles.size() * sizeof(PsRole));
-  if (n_res > 0) a.res_role = a.role_off + role_off.size();
-  a.n_logits_roles = n_lg;
+  if (n_res > 0) a.res_role = a.role_off + (grid + 1);
+  a.n_logits_roles = s->ps_setup_n_lg;
   a.n_layer = NL; a.n_rows = W; a.S = S; a.d = d; a.n_head = H; a.nb_mlp = NB;
   a.n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;
   a.ctl = s->ps_ctl.as<int>(); a.step0 = s->step; a.n_steps = n_forced + max_depth; a.mask_until_len = mask_until_len;
   a.n_forced = n_forced;
   for (int i = 0; i < n_forced; i++) a.forced[i] = forced[i];
   a.g_xn = s->ps_gxn.p;
-  a.x_fin = gxb[xi]; a.P2 = s->ps_gp2.p; a.b2_last = m->dec[NL - 1].mlp2.b; a.tag_base = tag_base;
+  a.x_fin = gxb[(3 * NL) & 1]; a.P2 = s->ps_gp2.p; a.b2_last = m->dec[NL - 1].mlp2.b; a.tag_base = tag_base;
   a.ln_g = m->ln_dec.g; a.ln_b = m->ln_dec.b; a.ln_eps = m->ln_dec.eps; a.ln_inside = m->ln_eps_inside_sqrt;
   a.Et = m->tok_emb_t; a.vocab_ld = m->vocab_ld; a.V = V; a.mask = s->mask.as<float>();
   a.tstats = s->ps_tstats.as<float>(); a.n_tiles = n_tiles;
@@ -194,8 +254,7 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   // first step of the chain: token + position embedding of the last prompt token (every later step: the merge role)
   launch_dec_prepare(st, reinterpret_cast<const int*>(s->host_block_dev), s->state.as<int>(), L, W, s->tabs.as<int>(),
                      s->Lmax, m->tok_emb, m->dec_pos, d, s->x.as<float>(), s->gctl.as<int>());
-  launch_ps_seed(st, s->x.as<float>(), W * d, gxb[0], tag_base + 1u);
-  WB_HIP(hipStreamSynchronize(st));            // (the staging vectors above are on the stack)
+  launch_ps_seed(st, s->x.as<float>(), W * d, gxb[0], tag_base + 1u, s->ps_ctl.as<int>());
   hipEvent_t e0 = nullptr, e1 = nullptr;
   prof_tag(KC_PERSIST, 0.0);                   // (its necessary bytes are known when the rows' lengths are: added by the caller)
   const bool timed = prof_take_events(&e0, &e1);
@@ -209,18 +268,23 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
     *steps_done = 0;
     return WB_OK;
   }
-  std::vector<int> ctl(n_ctl);
-  WB_HIP(hipMemcpyAsync(ctl.data(), s->ps_ctl.p, (size_t)n_ctl * 4, hipMemcpyDeviceToHost, st));
-  int gstep = 0;
-  WB_HIP(hipMemcpyAsync(&gstep, s->gctl.as<int>() + GC_STEP, 4, hipMemcpyDeviceToHost, st));
+  // what the host needs, into pinned memory, behind one synchronisation: the error word, the control block (GC_STEP: steps
+  // committed) and the token rows
+  int* hp = s->ps_pin;
+  s->ps_pin_busy = true;
+  WB_HIP(hipMemcpyAsync(hp + pin.err, s->ps_ctl.as<int>() + HX_ERR, 4, hipMemcpyDeviceToHost, st));
+  WB_HIP(hipMemcpyAsync(hp + pin.gctl, s->gctl.p, pin.ctl_ints * 4, hipMemcpyDeviceToHost, st));
+  WB_HIP(hipMemcpyAsync(hp + pin.tok, s->gtok.p, (pin.total - pin.tok) * 4, hipMemcpyDeviceToHost, st));
   WB_HIP(hipStreamSynchronize(st));
-  if (ctl[HX_ERR] != 0 && gstep == s->step) {  // nothing committed: the chain can take over from the same control block
+  s->ps_pin_busy = false;
+  const int err = hp[pin.err], gstep = hp[pin.gctl + GC_STEP];
+  if (err != 0 && gstep == s->step) {          // nothing committed: the chain can take over from the same control block
     s->ps_grid = 0;
     *fell_back = true;
     *steps_done = 0;
     return WB_OK;
   }
-  WB_REQUIRE(ctl[HX_ERR] == 0, WB_ERR_HIP, "persistent decode: a wait gave up (counter %d) at step %d", ctl[HX_ERR] - 1, gstep);
+  WB_REQUIRE(err == 0, WB_ERR_HIP, "persistent decode: a wait gave up (counter %d) at step %d", err - 1, gstep);
   if (n_stamps) {
     std::vector<unsigned long long> hs(n_stamps);
     WB_HIP(hipMemcpy(hs.data(), s->ps_stamps.p, n_stamps * 8, hipMemcpyDeviceToHost));
@@ -280,12 +344,19 @@ int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_
   // (= slot 0 of the next row, a prompt position nobody reads), so the buffer carries one extra slot
   WB_TRY(s->gtok.ensure(((size_t)S * s->Lmax + 1) * 4));
   std::vector<int> ctl(ctl_ints, 0);
-  auto seed_ctl = [&]() -> int {                     // the chain starts at the session's step with that position's prompt token
-    std::fill(ctl.begin(), ctl.end(), 0);
-    ctl[GC_STEP] = s->step;
-    for (int i = 0; i < W; i++) ctl[GC_HDR + i] = prompt[s->step];
-    WB_HIP(hipMemcpyAsync(s->gctl.p, ctl.data(), ctl_ints * 4, hipMemcpyHostToDevice, st));
-    WB_HIP(hipStreamSynchronize(st));
+  // the seed travels through the session's pinned words: the copy needs no wait for its source, so the persistent launch is
+  // enqueued behind the encoder instead of draining it (wait: the chain of one launch per sublayer synchronises as before)
+  const PsPin pin = ps_pin_layout(ctl_ints, (size_t)S * s->Lmax + 1);
+  WB_TRY(ps_pin_ensure(s, pin.total));
+  auto seed_ctl = [&](bool wait) -> int {            // the chain starts at the session's step with that position's prompt token
+    if (s->ps_pin_busy) { WB_HIP(hipStreamSynchronize(st)); s->ps_pin_busy = false; }
+    int* seed = s->ps_pin + pin.seed;
+    std::fill(seed, seed + ctl_ints, 0);
+    seed[GC_STEP] = s->step;
+    for (int i = 0; i < W; i++) seed[GC_HDR + i] = prompt[s->step];
+    s->ps_pin_busy = true;
+    WB_HIP(hipMemcpyAsync(s->gctl.p, seed, ctl_ints * 4, hipMemcpyHostToDevice, st));
+    if (wait) { WB_HIP(hipStreamSynchronize(st)); s->ps_pin_busy = false; }
     return WB_OK;
   };
   const StepPlan plan = plan_step(s, W, false);     // (no 9 - 16-row fused bucket here: W in 9..16 is batch mode)
@@ -302,18 +373,18 @@ int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_
   int n_forced = 0;
   if (persist && sw::persist_prefill() && s->step == 0 && n_forced_max <= PS_MAX_FORCED && s->has_mask) n_forced = n_forced_max;
   if (n_forced == 0) WB_TRY(host_prefill());
-  WB_TRY(seed_ctl());
+  WB_TRY(seed_ctl(!persist));
   ScopedTimer tm(st, 3);
   if (persist) {
     bool fell_back = false;
-    WB_TRY(run_persistent_chain(s, eot, max_depth, mask_until_len, prompt + s->step + 1, n_forced, &depth, &fell_back));
+    WB_TRY(run_persistent_chain(s, eot, max_depth, mask_until_len, prompt + s->step + 1, n_forced, pin, &depth, &fell_back));
     if (fell_back) {
       // rows whose merge role ran before the give-up have moved their control words: prefill on the host (if the launch was
       // to do it) and start the chain over from the seed
       persist = false;
       depth = 0;
       WB_TRY(host_prefill());
-      WB_TRY(seed_ctl());
+      WB_TRY(seed_ctl(true));
       n_forced = 0;
     } else {
       if (profile().on) profile().ms[4] += depth;
@@ -439,10 +510,18 @@ int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_
   }
   }   // (!persist)
   tm.stop();
-  std::vector<int> toks((size_t)S * s->Lmax + 1);
-  WB_HIP(hipMemcpyAsync(ctl.data(), s->gctl.p, ctl_ints * 4, hipMemcpyDeviceToHost, st));
-  WB_HIP(hipMemcpyAsync(toks.data(), s->gtok.p, toks.size() * 4, hipMemcpyDeviceToHost, st));
-  WB_HIP(hipStreamSynchronize(st));
+  std::vector<int> toks_chain;
+  const int* toks = s->ps_pin + pin.tok;             // (the persistent launch left control block and token rows in ps_pin)
+  if (persist) {
+    std::copy(s->ps_pin + pin.gctl, s->ps_pin + pin.gctl + ctl_ints, ctl.begin());
+  } else {
+    toks_chain.resize((size_t)S * s->Lmax + 1);
+    WB_HIP(hipMemcpyAsync(ctl.data(), s->gctl.p, ctl_ints * 4, hipMemcpyDeviceToHost, st));
+    WB_HIP(hipMemcpyAsync(toks_chain.data(), s->gtok.p, toks_chain.size() * 4, hipMemcpyDeviceToHost, st));
+    WB_HIP(hipStreamSynchronize(st));
+    s->ps_pin_busy = false;
+    toks = toks_chain.data();
+  }
   tm.collect();
   WB_TRY(dec_split_check(s));
   WB_REQUIRE(ctl[GC_BAD] == 0, WB_ERR_STATE, "a decode step produced a row without a finite log-prob (NaN logits: non-finite "

@@ -140,30 +140,45 @@ struct CrossLds {
 };
 
 // ---- resident operands (persistent kernel only) -------------------------------------------------------------------------
-// A block that runs the SAME self- or cross-attention role every step keeps RS float4 per thread of that role's step-invariant
-// operands in LDS for the whole launch: slot s of thread tid lives at res[s * 512 + tid].  A thread reads back only what it
-// wrote itself (no barrier; consecutive lanes sit 16 bytes apart) and every product keeps its operands and its place in the
-// sum, so the bits are those of the streamed path.  What goes in is what the streamed path requests AFTER its wait:
-//   self-attention   QKV weight rounds 2 .. 2 + NRND - 1 (rounds 0 and 1 are in registers before the wait), then NWO_A rows of
-//                    the thread's Wo slice
-//   cross-attention  the V rows of the leading NVT key tiles in the ring's kv[t][i] order (one key pass only: the two-pass
-//                    ring refills its registers with the second pass's K first, and its body is left exactly as it was: it
-//                    sits at the register limit), then NWO_X rows of the Wo slice
+// A block that runs the SAME self- or cross-attention role every step keeps RS x 512 float4 of that role's step-invariant
+// operands in LDS for the whole launch.  Only the lanes that HOLD an operand own slots: slot s of holder k (of NH holders) of
+// an operand lives at res[base + s * NH + k].  A holder reads back only what it wrote itself (no barrier; consecutive holders
+// sit 16 bytes apart) and every product keeps its operands and its place in the sum, so the bits are those of the streamed
+// path.  (A lane that holds nothing -- its loads are never consumed in the streamed path either -- reads the slot of one
+// that does: every address stays inside the region, nothing is stored there.)  What goes in is what the streamed path
+// requests AFTER its wait:
+//   self-attention   QKV weight rounds 2 .. 2 + NRND - 1 (rounds 0 and 1 are in registers before the wait) for the QL = 8 x 48
+//                    lanes with seg < 3, then NWO_A rows of the Wo slice for the WL threads with jg < G
+//   cross-attention  the V rows of the leading NVT key tiles in the ring's kv[t][i] order, all 512 threads (one key pass only:
+//                    the two-pass ring refills its registers with the second pass's K first, and its body is left exactly as
+//                    it was: it sits at the register limit), then NWO_X rows of the Wo slice for the WL threads with jg < G
+// Rounds come first (they sit on the token's critical path, the Wo rows are consumed last): d = 384 takes two of its four
+// post-wait rounds -- the two that are left are requested together when rounds 0 and 1 are consumed and land under the LDS
+// rounds -- d = 512 stays at the one round it was measured with and gains Wo rows from the packing.
 template <int DPL, int NP, int RS>
 struct ResGeom {
   static constexpr int d = 64 * DPL, G = d / 4 <= 32 ? 8 : 4, RPG = 64 / G;
   static constexpr int KW = d / 8, RK = DPL >= 6 ? 8 : 16, NIT = KW / RK;         // (dec_attn_body's weight rounds)
-  static constexpr int NRND = (NIT - 2 < RS / RK ? NIT - 2 : RS / RK) > 0 ? (NIT - 2 < RS / RK ? NIT - 2 : RS / RK) : 0;
-  static constexpr int WO_A = NRND * RK;                                           // first Wo slot of the self-attention role
-  static constexpr int NWO_A = RS - WO_A < RPG ? RS - WO_A : RPG;
+  static constexpr int CAP = RS * ROLE_NT;                                         // float4 of the region
+  static constexpr int QL = 8 * 48;                                                // lanes that hold QKV weights: seg < 3 of every wave
+  static constexpr int WL = G * (d / 4) < ROLE_NT ? G * (d / 4) : ROLE_NT;         // threads that hold Wo rows: jg < G
+  static constexpr int NRND_MAX = DPL == 6 ? 2 : 1;
+  static constexpr int NRND_FIT = CAP / (RK * QL) < NIT - 2 ? CAP / (RK * QL) : NIT - 2;
+  static constexpr int NRND = NRND_FIT <= 0 ? 0 : (NRND_FIT < NRND_MAX ? NRND_FIT : NRND_MAX);
+  static constexpr int WO_A = NRND * RK * QL;                                      // float4 offset of the self-attention role's Wo rows
+  static constexpr int NWO_A = (CAP - WO_A) / WL < RPG ? (CAP - WO_A) / WL : RPG;
   static constexpr int SL = 4, NTILE = CROSS_FUSED_MAX_C / 128;                    // (dec_cross_body's key ring)
   static constexpr int NVT = NP > 1 ? 0 : (RS / SL < NTILE ? RS / SL : NTILE);
-  static constexpr int WO_X = NVT * SL;
-  static constexpr int NWO_X = NP > 1 ? 0 : (RS - WO_X < RPG ? RS - WO_X : RPG);
-  static_assert(RS >= 0 && WO_A + NWO_A <= RS && WO_X + NWO_X <= RS, "resident slots");
+  static constexpr int WO_X = NVT * SL * ROLE_NT;                                  // ... of the cross-attention role's
+  static constexpr int NWO_X = NP > 1 ? 0 : ((CAP - WO_X) / WL < RPG ? (CAP - WO_X) / WL : RPG);
+  static_assert(RS >= 0 && WO_A + NWO_A * WL <= CAP && WO_X + NWO_X * WL <= CAP, "resident region");
+  // holder index of a thread: its own if it holds the operand, else the last holder's (never consumed)
+  static __device__ __forceinline__ int q_holder(int wave, int lane) { return wave * 48 + (lane < 47 ? lane : 47); }
+  static __device__ __forceinline__ int wo_holder(int tid) { return tid < WL - 1 ? tid : WL - 1; }
 };
-__device__ __forceinline__ float4 res_ld(const float4* res, int slot, int tid) { return res[slot * ROLE_NT + tid]; }
-__device__ __forceinline__ void res_st(float4* res, int slot, int tid, const float4& v) { res[slot * ROLE_NT + tid] = v; }
+// slot `slot` of holder k of an operand with NH holders whose first float4 is `base`
+__device__ __forceinline__ float4 res_ld(const float4* res, int base, int NH, int slot, int k) { return res[base + slot * NH + k]; }
+__device__ __forceinline__ void res_st(float4* res, int base, int NH, int slot, int k, const float4& v) { res[base + slot * NH + k] = v; }
 
 __device__ __forceinline__ float gelu_erf_f(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
@@ -877,7 +892,7 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
           for (int q = 0; q < RG::NRND; q++) {
             float4 wl[RK];
 #pragma unroll
-            for (int j = 0; j < RK; j++) wl[j] = res_ld(res, q * RK + j, tid);
+            for (int j = 0; j < RK; j++) wl[j] = res_ld(res, 0, RG::QL, q * RK + j, RG::q_holder(wave, lane));
             const int kb = RK * (2 + q);
 #pragma unroll
             for (int j = 0; j < RK; j++) {
@@ -1009,7 +1024,7 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   if constexpr (RG::NWO_A > 0) {
     if (res != nullptr) {
 #pragma unroll
-      for (int i = 0; i < RG::NWO_A; i++) wo[i] = res_ld(res, RG::WO_A + i, tid);
+      for (int i = 0; i < RG::NWO_A; i++) wo[i] = res_ld(res, RG::WO_A, RG::WL, i, RG::wo_holder(tid));
     }
   }
   float ov[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1063,7 +1078,8 @@ __device__ __forceinline__ void dec_attn_res_fill(const AttnFusedArgs& a, const 
 #pragma unroll
     for (int j = 0; j < RK; j++) w[j] = ld_w4(wq + (int64_t)(RK * (2 + q) + j) * a.ldqkv);
 #pragma unroll
-    for (int j = 0; j < RK; j++) res_st(res, q * RK + j, tid, w[j]);
+    for (int j = 0; j < RK; j++)
+      if (seg < 3) res_st(res, 0, RG::QL, q * RK + j, RG::q_holder(wave, lane), w[j]);
   }
   if constexpr (RG::NWO_A > 0) {
     const int cf = tid % CF, jg = tid / CF;
@@ -1073,7 +1089,8 @@ __device__ __forceinline__ void dec_attn_res_fill(const AttnFusedArgs& a, const 
 #pragma unroll
     for (int i = 0; i < RG::NWO_A; i++) w[i] = ld_w4(wp + (int64_t)i * d);
 #pragma unroll
-    for (int i = 0; i < RG::NWO_A; i++) res_st(res, RG::WO_A + i, tid, w[i]);
+    for (int i = 0; i < RG::NWO_A; i++)
+      if (jg < G) res_st(res, RG::WO_A, RG::WL, i, tid, w[i]);
   }
 }
 
@@ -1360,7 +1377,7 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
         for (int i = 0; i < SL; i++) {
           const int k0 = t * KT + rgp + 32 * i, key = p * PASS_C + k0;
           const float pk = key < C ? pbuf[key] : 0.f;
-          if (t < RG::NVT) { if (res_v) kv[t][i] = res_ld(res, t * SL + i, tid); }
+          if (t < RG::NVT) { if (res_v) kv[t][i] = res_ld(res, 0, ROLE_NT, t * SL + i, tid); }
           o.x += pk * kv[t][i].x; o.y += pk * kv[t][i].y; o.z += pk * kv[t][i].z; o.w += pk * kv[t][i].w;
           if (p + 1 < NP)                           // the register takes the V row of the next pass's key
             kv[t][i] = gld4(Vh + (min(key + PASS_C, C - 1) * a.ldkv + c4));
@@ -1382,7 +1399,7 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
   if constexpr (RG::NWO_X > 0) {
     if (res != nullptr) {
 #pragma unroll
-      for (int i = 0; i < RG::NWO_X; i++) wo[i] = res_ld(res, RG::WO_X + i, tid);
+      for (int i = 0; i < RG::NWO_X; i++) wo[i] = res_ld(res, RG::WO_X, RG::WL, i, RG::wo_holder(tid));
     }
   }
   float ov[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1431,7 +1448,7 @@ __device__ __forceinline__ void dec_cross_res_fill(const CrossFusedArgs& a, cons
 #pragma unroll
       for (int i = 0; i < SL; i++) v[i] = gld4(Vh + (min(t * KT + rg + 32 * i, C - 1) * a.ldkv + c4));
 #pragma unroll
-      for (int i = 0; i < SL; i++) res_st(res, t * SL + i, tid, v[i]);
+      for (int i = 0; i < SL; i++) res_st(res, 0, ROLE_NT, t * SL + i, tid, v[i]);
     }
   }
   if constexpr (RG::NWO_X > 0) {
@@ -1442,7 +1459,8 @@ __device__ __forceinline__ void dec_cross_res_fill(const CrossFusedArgs& a, cons
 #pragma unroll
     for (int i = 0; i < RG::NWO_X; i++) w[i] = ld_w4(wp + (int64_t)i * d);
 #pragma unroll
-    for (int i = 0; i < RG::NWO_X; i++) res_st(res, RG::WO_X + i, tid, w[i]);
+    for (int i = 0; i < RG::NWO_X; i++)
+      if (jg < G) res_st(res, RG::WO_X, RG::WL, i, tid, w[i]);
   }
 }
 

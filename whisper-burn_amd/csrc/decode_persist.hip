@@ -481,8 +481,10 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
   }
 }
 
-// the first step's x rows (dec_prepare_kernel wrote plain floats) as granules with the tag attn(0) of step 0 expects
-__global__ void ps_seed_kernel(const float* __restrict__ x, int n, void* gx, unsigned tag) {
+// the first step's x rows (dec_prepare_kernel wrote plain floats) as granules with the tag attn(0) of step 0 expects; the
+// launch's stop word starts at "never" (the rest of the control block was zeroed on the stream in front of this kernel)
+__global__ void ps_seed_kernel(const float* __restrict__ x, int n, void* gx, unsigned tag, int* ctl) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctl[HX_STOP] = INT_MAX;
   const Buf16 b(gx);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) st_gran(b, (uint32_t)i, tag, x[i]);
 }
@@ -505,6 +507,22 @@ int dec_persist_resident_slots(int d, int n_rows, int max_keys) {
   WB_PS_INSTANCES(WB_PS_SLOTS)
 #undef WB_PS_SLOTS
   return 0;
+}
+
+// the resident geometry of that instance: out = {RS, NRND, NWO_A, NVT, NWO_X} (decode_fused_bodies.h: ResGeom); false: no instance
+bool dec_persist_resident_geometry(int d, int n_rows, int max_keys, int out[5]) {
+  if (!dec_persist_supported(d, n_rows, max_keys)) return false;
+  const int dpl = d / 64, mr = n_rows > 4 ? 8 : 4, np = max_keys > CROSS_FUSED_MAX_C ? 2 : 1;
+#define WB_PS_GEOM(DPL_, MR_, NP_)                                                            \
+  if (dpl == DPL_ && mr == MR_ && np == NP_) {                                                \
+    using RG = ResGeom<DPL_, NP_, PsArena<DPL_, MR_, NP_>::RS>;                               \
+    out[0] = PsArena<DPL_, MR_, NP_>::RS; out[1] = RG::NRND; out[2] = RG::NWO_A; out[3] = RG::NVT; out[4] = RG::NWO_X; \
+    if (PsArena<DPL_, MR_, NP_>::RS == 0) out[1] = out[2] = out[3] = out[4] = 0;              \
+    return true;                                                                              \
+  }
+  WB_PS_INSTANCES(WB_PS_GEOM)
+#undef WB_PS_GEOM
+  return false;
 }
 
 int ps_ctl_ints(int S, int n_layer) { return HX_HDR + (S + n_layer * S + 2 * n_layer + 8 + PS_NGO + 1) * HX_LINE; }
@@ -537,8 +555,8 @@ int dec_persist_max_grid(int device, int d, int n_rows, int max_keys) {
   return cus * 1;
 }
 
-void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned tag) {
-  hipLaunchKernelGGL(ps_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, n, gx, tag);
+void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned tag, int* ctl) {
+  hipLaunchKernelGGL(ps_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, n, gx, tag, ctl);
 }
 
 int launch_dec_persist(hipStream_t st, const PersistArgs& a, int grid) {

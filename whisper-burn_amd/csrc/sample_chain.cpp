@@ -200,6 +200,14 @@ int wb_session_last_samples(wb_session* s, int32_t* tokens, int32_t row_stride, 
 
 int wb_session_graph_count(const wb_session* s) { return s ? (int)s->graphs.size() : 0; }
 int64_t wb_session_graph_captures(const wb_session* s) { return s ? s->n_captures : 0; }
+int wb_persist_resident_geometry(int32_t n_state, int32_t n_rows, int32_t max_keys, int32_t* out5) {
+  WB_REQUIRE(out5, WB_ERR_ARG, "wb_persist_resident_geometry: null argument");
+  int g[5] = {0, 0, 0, 0, 0};
+  WB_REQUIRE(dec_persist_resident_geometry(n_state, n_rows, max_keys, g), WB_ERR_SHAPE,
+             "wb_persist_resident_geometry: no persistent instance serves n_state %d with %d rows and %d keys", n_state, n_rows, max_keys);
+  for (int i = 0; i < 5; i++) out5[i] = g[i];
+  return WB_OK;
+}
 
 int wb_session_decode_sample(wb_session* s, const wb_decode_params* p, const wb_sample_params* sp, const int32_t* prompt,
                              int32_t prompt_len, const uint8_t* active, const int32_t* stream_ids, int32_t* out_tokens,

@@ -303,6 +303,7 @@ wb_session::~wb_session() {
   if (host_block) (void)hipHostFree(host_block);
   if (guard_host) (void)hipHostFree(guard_host);
   if (pcm_stage) (void)hipHostFree(pcm_stage);
+  if (ps_pin) (void)hipHostFree(ps_pin);
   if (ev_seg) (void)hipEventDestroy(ev_seg);
   if (st2) (void)hipStreamDestroy(st2);
   if (st) (void)hipStreamDestroy(st);

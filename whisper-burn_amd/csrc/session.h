@@ -38,6 +38,16 @@ struct wb_session {
   wb::DevMem ps_gx, ps_gpa, ps_gpc, ps_gp2, ps_gxn;     // ... its residual streams / planes as 8-byte {tag, value} granules
   unsigned ps_launches = 0;                     // launches so far: the high half of the granule tags
   int ps_grid = -1;                                                    // co-resident blocks for this model (-1: not asked yet)
+  // Launch setup of the persistent kernel (decode_chain.cpp: ps_setup_ensure): the per-layer argument blocks (ps_layers) and
+  // the dealt role tables (ps_roles) stay on the device while ps_setup_key -- everything they were built from -- stands.
+  // Same rule as wins_host / meta_host / mask_host: the key is voided before the contents change.
+  std::vector<uint64_t> ps_setup_key;
+  std::vector<wb::PsRole> ps_roles_host;        // the dealt roles (the stamps file names them)
+  int ps_setup_grid = 0, ps_setup_n_lg = 0, ps_setup_n_res = 0;
+  // pinned host words of a greedy call: [0, ps_pin_back) the control block's seed (host -> device), then what the host reads
+  // after the launch (the error word, the control block, the token rows) behind ONE synchronisation
+  int* ps_pin = nullptr; size_t ps_pin_ints = 0;
+  bool ps_pin_busy = false;                     // a copy out of / into ps_pin may be in flight (no synchronisation since)
   int n_tiles_v = 0, ct_v = 128;
   int ks_qkv = 1, ksl_qkv = 0, ks_o = 1, ksl_o = 0, ks_1 = 1, ksl_1 = 0, ks_2 = 1, ksl_2 = 0, ks_v = 1, ksl_v = 0;
   wb::DevMem bc_ctl, bc_topk;   // device-chained beam search (decode.h: BeamChainArgs): control block, top-k rows of the step
