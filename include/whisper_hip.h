@@ -494,6 +494,13 @@ int64_t wb_session_graph_captures(const wb_session* s);
  * of the self-attention role, resident V tiles and resident Wo rows of the cross-attention role}.  Needs no device.
  * WB_ERR_SHAPE if no instance serves the shape. */
 int wb_persist_resident_geometry(int32_t n_state, int32_t n_rows, int32_t max_keys, int32_t* out5);
+/* Debug / tests: one step's roles of the persistent greedy kernel as they are dealt to a grid of `grid` blocks (clamped to
+ * the roles of a step) -- per role, grouped by block, out_kinds = kind | layer << 8 | row << 16 (kind: 0 self-attention,
+ * 1 cross-attention, 2 MLP, 3 logits, 4 merge, 5 final LayerNorm; the encoding of the WHISPER_HIP_PS_STAMPS file) and
+ * out_block = its block.  legacy != 0: the dealing of WHISPER_HIP_PERSIST_DEAL=legacy.  Needs no device.  Returns the
+ * number of roles (at most cap), or a negative status: WB_ERR_SHAPE if no instance serves the shape. */
+int wb_persist_role_plan(int32_t n_layer, int32_t n_head, int32_t n_state, int32_t n_rows, int32_t n_vocab, int32_t grid,
+                         int32_t legacy, int32_t* out_kinds, int32_t* out_block, int32_t cap);
 /* best_of independent sampled sequences per window from `prompt`, on a fresh or rewound session; the draw and the row
  * bookkeeping run on the device, chunks of steps replay as one graph (the same graph for every temperature and seed).
  * active [W] (NULL = all): windows with active[w] == 0 are not decoded and nothing of theirs is written.

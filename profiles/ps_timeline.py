@@ -3,6 +3,9 @@
 Per role kind and layer, over the roles of LIVE rows only (a row whose window has ended skips its attention roles): the
 time from role start to the wait being passed, the phases after the wait, and the arrive; per step, the critical chain.
 Stamp slots: 0 role start, 1 wait passed, 2-5 phases inside the role, 6 done, 7 arrived.  Clock: 100 MHz (10 ns ticks).
+Below the table, for the attn, cross, finln and merge rows: min / median / max OVER THE ROLES of the kind (each role's mean over
+the steps) of "wait passed @" and "done @" relative to the step start -- a stage whose roles fall in two groups shows here and
+not in a mean -- and, when the file carries role_off behind the stamps (files written since R15), each role's block.
     python profiles/ps_timeline.py stamps.bin [first_step last_step] [row]"""
 import sys
 
@@ -11,7 +14,13 @@ import numpy as np
 raw = np.fromfile(sys.argv[1], dtype=np.uint8)
 n_steps, n_roles, grid, ns = [int(x) for x in raw[:16].view(np.int32)]
 kinds = raw[16:16 + 4 * n_roles].view(np.int32)
-st = raw[16 + 4 * n_roles:].view(np.uint64).reshape(n_steps, n_roles, ns).astype(np.float64)
+n_st = 8 * n_steps * n_roles * ns
+st = raw[16 + 4 * n_roles:16 + 4 * n_roles + n_st].view(np.uint64).reshape(n_steps, n_roles, ns).astype(np.float64)
+tail = raw[16 + 4 * n_roles + n_st:]                # optional: marker "ROff", then role_off [grid + 1]
+block = None
+if len(tail) >= 4 * (grid + 2) and int(tail[:4].view(np.int32)[0]) == 0x66664f52:
+    role_off = tail[4:4 * (grid + 2)].view(np.int32)
+    block = np.searchsorted(role_off, np.arange(n_roles), side="right") - 1
 st[st == 0] = np.nan
 names = {0: "attn", 1: "cross", 2: "mlp", 3: "logits", 4: "merge", 5: "finln"}
 kind, layer, row = kinds & 0xff, (kinds >> 8) & 0xff, kinds >> 16
@@ -28,6 +37,7 @@ step_end = np.nanmax(merge_done, axis=1)
 step_start = np.concatenate([[np.nan], step_end[:-1]])
 hdr = f"{'role':<10}{'n':>4}{'wait':>8}{'w->p2':>8}{'p2->p3':>8}{'p3->p4':>8}{'p4->p5':>8}{'p5->done':>9}{'arrive':>8}{'run':>8}{'done@':>9}{'arrived@':>9}"
 print(hdr)
+spread = []
 for k in (0, 1, 2, 5, 3, 4):
     for l in sorted(set(layer[kind == k])):
         cols = (kind == k) & (layer == l)
@@ -42,6 +52,29 @@ for k in (0, 1, 2, 5, 3, 4):
         rel_done = np.nanmean((np.nanmax(s[:, :, 6], axis=1) - step_start) * tick)
         rel_arr = np.nanmean((np.nanmax(s[:, :, 7], axis=1) - step_start) * tick)
         nm = names[k] + (f" L{l}" if k < 3 else "")
+        if k in (0, 1, 3, 4, 5):                    # per role: mean over the steps of (stamp - step start)
+            wp = np.nanmean((s[:, :, 1] - step_start[:, None]) * tick, axis=0)
+            dn = np.nanmean((s[:, :, 6] - step_start[:, None]) * tick, axis=0)
+            spread.append((nm, wp, dn, block[cols] if block is not None else None))
         print(f"{nm:<10}{int(cols.sum()):>4}{d(0,1):>8.2f}{d(1,2):>8.2f}{d(2,3):>8.2f}{d(3,4):>8.2f}{d(4,5):>8.2f}{d(5,6):>9.2f}{d(6,7):>8.2f}{d(1,6):>8.2f}{rel_done:>9.2f}{rel_arr:>9.2f}")
 dd = np.diff(step_end) * tick
 print(f"step time (merge arrived -> next merge arrived): mean {np.nanmean(dd):.2f} us, median {np.nanmedian(dd):.2f}, min {np.nanmin(dd):.2f}, max {np.nanmax(dd):.2f}")
+print("over the roles of a kind (each role: mean over the steps), us after the step start (merge: of its own step's start):")
+print(f"{'role':<10}{'n':>4}  {'wait passed @  min / median / max':<36}{'done @  min / median / max':<34}")
+for nm, wp, dn, blk in spread:
+    f3 = lambda v: f"{np.nanmin(v):8.2f} /{np.nanmedian(v):8.2f} /{np.nanmax(v):8.2f}"
+    print(f"{nm:<10}{len(wp):>4}  {f3(wp):<36}{f3(dn):<34}")
+    if nm == "logits" and blk is not None:          # the last to finish, and what else their blocks hold
+        late = np.argsort(-np.nan_to_num(dn))[:12]
+        def held(b):
+            o = [names[kind[i]] + f" L{layer[i]}" for i in np.nonzero(block == b)[0] if kind[i] < 3]
+            return "+".join(o) if o else "-"
+        print(f"{'':<10}last to finish (block [its layer roles]: wait passed @ / done @)  " +
+              "  ".join(f"b{blk[i]}[{held(blk[i])}]:{wp[i]:.2f}/{dn[i]:.2f}" for i in late))
+        behind = np.array([held(b) != "-" for b in blk])
+        for lab, m in (("behind a layer role", behind), ("on blocks without one", ~behind)):
+            if m.any():
+                print(f"{'':<10}{lab}: n {int(m.sum())}, done @ min / median / max {np.nanmin(dn[m]):.2f} / {np.nanmedian(dn[m]):.2f} / {np.nanmax(dn[m]):.2f}")
+    if nm in ("attn L0", "merge", "finln"):
+        per = "  ".join((f"b{blk[i]}:" if blk is not None else f"#{i}:") + f"{wp[i]:.2f}/{dn[i]:.2f}" for i in range(len(wp)))
+        print(f"{'':<10}per role (block: wait passed @ / done @)  {per}")

@@ -157,6 +157,8 @@ extern "C" {
     pub fn wb_session_graph_count(s: *const wb_session) -> c_int;
     pub fn wb_session_graph_captures(s: *const wb_session) -> i64;
     pub fn wb_persist_resident_geometry(n_state: i32, n_rows: i32, max_keys: i32, out5: *mut i32) -> c_int;
+    pub fn wb_persist_role_plan(n_layer: i32, n_head: i32, n_state: i32, n_rows: i32, n_vocab: i32, grid: i32, legacy: i32,
+                                out_kinds: *mut i32, out_block: *mut i32, cap: i32) -> c_int;
     pub fn wb_session_last_samples(s: *mut wb_session, tokens: *mut i32, row_stride: i32, lens: *mut i32) -> c_int;
     pub fn wb_sample_rows(device: c_int, logits: *const c_float, R: i32, ld: i32, V: i32, mask: *const c_float,
                           row_masked: *const u8, row_stats: *const c_float, temperature: c_float, seed: u64, attempt: i32,

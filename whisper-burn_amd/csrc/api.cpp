@@ -344,4 +344,24 @@ int wb_forward(wb_model* m, const float* mel, int B, int T, const int32_t* token
   return decoder_common(m, sc, st, tokens, B, L, sc->io_b.as<float>(), C, logits);
 }
 
+int wb_persist_role_plan(int32_t n_layer, int32_t n_head, int32_t n_state, int32_t n_rows, int32_t n_vocab, int32_t grid,
+                         int32_t legacy, int32_t* out_kinds, int32_t* out_block, int32_t cap) {
+  WB_REQUIRE(out_kinds && out_block, WB_ERR_ARG, "wb_persist_role_plan: null argument");
+  WB_REQUIRE(n_layer > 0 && n_head > 0 && n_rows > 0 && n_vocab > 0 && grid > 0, WB_ERR_ARG, "wb_persist_role_plan: bad argument");
+  WB_REQUIRE(dec_persist_supported(n_state, n_rows, 750), WB_ERR_SHAPE,
+             "wb_persist_role_plan: no persistent instance serves n_state %d with %d rows", n_state, n_rows);
+  const int NB = dec_mlp_fused_planes(n_state), n_tiles = (n_vocab + 127) / 128;
+  const int g = std::max(1, std::min((int)grid, n_layer * (2 * n_rows * n_head + NB) + n_tiles + 2 * n_rows));   // (ps_setup_ensure)
+  const PsDeal deal = ps_deal_roles(n_layer, n_head, n_rows, NB, n_tiles, g, legacy ? PS_DEAL_LEGACY : PS_DEAL_SLACK, false);
+  const int n = (int)deal.roles.size();
+  WB_REQUIRE(n <= cap, WB_ERR_ARG, "wb_persist_role_plan: %d roles, room for %d", n, (int)cap);
+  for (int b = 0; b < g; b++)
+    for (int i = deal.role_off[b]; i < deal.role_off[b + 1]; i++) {
+      const PsRole& r = deal.roles[i];                // (the encoding of the stamps file, decode_chain.cpp)
+      out_kinds[i] = r.kind | ((r.kind <= PSR_MLP ? r.layer : 0) << 8) | ((r.kind == PSR_LOGITS ? 0 : r.b) << 16);
+      out_block[i] = b;
+    }
+  return n;
+}
+
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "kernels.h"
 #include "wb_internal.h"
@@ -317,6 +318,19 @@ struct PersistArgs {
   int* dead = nullptr;                        // [S]: rows whose window has ended
   unsigned long long* stamps = nullptr;       // optional timeline: [n_steps][n_roles][3] (role start, wait passed, done)
 };
+// One step's roles dealt to the blocks (decode_chain.cpp; no device, no session).  Layer role i sits on block i % grid; the
+// policy decides where the final-LN, logits and merge roles go.  PS_DEAL_SLACK keeps merge(r) and finln(r) off the blocks
+// that hold a first-layer self- or cross-attention role (they must be back at their wait, operands requested, before the
+// step ends); PS_DEAL_LEGACY puts them on the least loaded blocks.  Every block's list is a subsequence of the one global
+// dependency order (layer roles by layer and sublayer, finln, logits, merge).
+enum { PS_DEAL_SLACK = 0, PS_DEAL_LEGACY = 1 };
+struct PsDeal {
+  std::vector<PsRole> roles;                  // grouped by block
+  std::vector<int> role_off;                  // [grid + 1]
+  std::vector<int> res_role;                  // [grid]: PersistArgs::res_role (all -1 with res_on false)
+  int n_lg = 0, n_res = 0;
+};
+PsDeal ps_deal_roles(int n_layer, int n_head, int n_rows, int nb_mlp, int n_tiles, int grid, int policy, bool res_on);
 int ps_ctl_ints(int S, int n_layer);
 bool dec_persist_supported(int d, int n_rows, int max_keys);
 int dec_persist_resident_slots(int d, int n_rows, int max_keys);   // resident float4 slots per thread; 0: nothing useful fits

@@ -2,6 +2,7 @@
 // launch per sublayer behind it.
 #include <climits>
 #include <cstring>
+#include <string>
 
 #include "decode_step.h"
 #include "handoff.h"
@@ -28,10 +29,121 @@ static int ps_pin_ensure(wb_session* s, size_t ints) {
   return WB_OK;
 }
 
+// One step's roles, dealt to the blocks: every block runs its own list, in dependency order, every step (decode.h).
+//
+// A block that holds a first-layer self- or cross-attention role ("early") is the first to be needed in the next step: it
+// should be back at its wait, weights and cached K/V requested, before this step ends.  A role of the step's tail on such
+// a block delays those requests to the step boundary, and the block's counter poll then queues behind them (vector loads
+// return in order).  PS_DEAL_LEGACY dealt finln and merge to "the least loaded blocks", which on a full grid are blocks
+// 0 .. W - 1 for the merge roles -- the self-attention roles of row 0's first heads.  PS_DEAL_SLACK: merge(r) goes behind
+// finln(r) (that role requests only LayerNorm parameters before its wait, so starting it at the step boundary costs
+// nothing), else to a block that is not early and holds no logits role, else to any block that is not early; finln
+// prefers blocks that are not early in the same way.  Only where every block is early (small grids) the least loaded ones.
+PsDeal ps_deal_roles(int NL, int H, int W, int NB, int n_tiles, int grid, int policy, bool res_on) {
+  std::vector<PsRole> lr;                            // the layer roles in dependency order
+  for (int l = 0; l < NL; l++) {
+    for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_ATTN, l, h, r});
+    for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_CROSS, l, h, r});
+    for (int j = 0; j < NB; j++) lr.push_back(PsRole{PSR_MLP, l, j, 0});
+  }
+  std::vector<std::vector<PsRole>> deal(grid);
+  for (size_t i = 0; i < lr.size(); i++) deal[i % grid].push_back(lr[i]);
+  // logits: blocks that hold a first-layer attention role stay free of it (see above).  Every logits block takes a run of
+  // consecutive 128-column tiles behind ONE fold + LayerNorm.
+  std::vector<char> early(grid, 0);
+  std::vector<int> cand;
+  for (int b = 0; b < grid; b++) {
+    for (const PsRole& r : deal[b]) early[b] |= r.layer == 0 && (r.kind == PSR_ATTN || r.kind == PSR_CROSS);
+    if (!early[b]) cand.push_back(b);
+  }
+  if ((int)cand.size() * 4 < n_tiles) { cand.clear(); for (int b = 0; b < grid; b++) cand.push_back(b); }
+  const bool slack = policy != PS_DEAL_LEGACY;
+  // blocks by load (stable: the lower block first); with `slack`, the ones that are not early before the early ones
+  auto by_load = [&](std::vector<int>& v) {
+    std::stable_sort(v.begin(), v.end(), [&](int x, int y) {
+      if (slack && early[x] != early[y]) return early[x] < early[y];
+      return deal[x].size() < deal[y].size();
+    });
+  };
+  // final LayerNorm (one per row): blocks without any layer role if there are some (they sit between the last MLP and
+  // the logits on the critical path), else the least loaded ones; they take no logits work
+  std::vector<int> fin_block(W, 0);
+  std::vector<char> is_fin(grid, 0);
+  {
+    std::vector<int> order(grid);
+    for (int b = 0; b < grid; b++) order[b] = b;
+    by_load(order);
+    for (int r = 0; r < W; r++) { fin_block[r] = order[r % grid]; deal[fin_block[r]].push_back(PsRole{PSR_FINLN, 0, 0, r}); is_fin[fin_block[r]] = 1; }
+  }
+  if ((int)cand.size() > 2 * W) cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int b) { return is_fin[b] != 0; }), cand.end());
+  std::stable_sort(cand.begin(), cand.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
+  const int tpb = (n_tiles + (int)cand.size() - 1) / (int)cand.size();
+  const int n_lg = (n_tiles + tpb - 1) / tpb;
+  std::vector<char> has_lg(grid, 0);
+  for (int q = 0; q < n_lg; q++) {
+    deal[cand[q]].push_back(PsRole{PSR_LOGITS, q, q * tpb, std::min(tpb, n_tiles - q * tpb)});
+    has_lg[cand[q]] = 1;
+  }
+  // merge (one per row)
+  {
+    std::vector<int> order;
+    if (slack) {
+      for (int b = 0; b < grid; b++) if (!early[b] && !has_lg[b]) order.push_back(b);
+      if (order.empty()) for (int b = 0; b < grid; b++) if (!early[b]) order.push_back(b);
+    }
+    if (order.empty()) for (int b = 0; b < grid; b++) order.push_back(b);
+    by_load(order);
+    for (int r = 0; r < W; r++) {
+      const int b = slack && !early[fin_block[r]] ? fin_block[r] : order[r % (int)order.size()];
+      deal[b].push_back(PsRole{PSR_MERGE, 0, 0, r});
+    }
+  }
+  PsDeal out;
+  out.n_lg = n_lg;
+  out.role_off.assign(grid + 1, 0);
+  for (int b = 0; b < grid; b++) {
+    out.role_off[b] = (int)out.roles.size();
+    out.roles.insert(out.roles.end(), deal[b].begin(), deal[b].end());
+  }
+  out.role_off[grid] = (int)out.roles.size();
+  // Resident operands (WHISPER_HIP_PERSIST_RESIDENT, default on; "0": off; "log": on, and one line on stderr): a block whose
+  // list holds exactly ONE layer role, a self- or cross-attention one, runs that role every step -- the kernel keeps what
+  // fits of the role's step-invariant operands in the LDS the roles leave free.  Blocks with several layer roles (a grid
+  // smaller than the layer roles) would have to share the region: they run as before.
+  out.res_role.assign(grid, -1);                    // per block: the index of its resident role
+  if (res_on)
+    for (int b = 0; b < grid; b++) {
+      int n_lr = 0, at = -1;
+      for (int i = out.role_off[b]; i < out.role_off[b + 1]; i++)
+        if (out.roles[i].kind <= PSR_MLP) { n_lr++; at = i; }
+      if (n_lr == 1 && out.roles[at].kind != PSR_MLP) { out.res_role[b] = at; out.n_res++; }
+    }
+  return out;
+}
+
+// WHISPER_HIP_PERSIST_DEAL=log: where the roles of the step's tail went, one line per built setup
+static void ps_deal_log(const PsDeal& deal, int grid) {
+  std::string where[2];
+  int n_lg_blocks = 0;
+  for (int b = 0; b < grid; b++) {
+    bool lg = false;
+    for (int i = deal.role_off[b]; i < deal.role_off[b + 1]; i++) {
+      const int k = deal.roles[i].kind;
+      lg |= k == PSR_LOGITS;
+      if (k == PSR_MERGE || k == PSR_FINLN) {
+        std::string& w = where[k == PSR_FINLN];
+        w += (w.empty() ? "" : ",") + std::to_string(b);
+      }
+    }
+    n_lg_blocks += lg;
+  }
+  fprintf(stderr, "persist deal: merge on blocks %s; finln on %s; logits blocks %d\n", where[0].c_str(), where[1].c_str(), n_lg_blocks);
+}
+
 // The launch setup of the persistent kernel: the per-layer argument blocks -- exactly what enqueue_step hands the fused
 // sublayer kernels -- and one step's roles dealt to the blocks, on the device (ps_layers, ps_roles).  All of it is a function
-// of the model (and its LayerNorm variant), the session's buffers, W, the grid, the window geometry and the resident switch
-// (what varies from call to call travels by value in PersistArgs), so a pooled session in a transcription loop builds and
+// of the model (and its LayerNorm variant), the session's buffers, W, the grid, the window geometry, the resident switch and the dealing
+// policy (what varies from call to call travels by value in PersistArgs), so a pooled session in a transcription loop builds and
 // uploads it once: it is kept under a key that names everything it was built from.  WHISPER_HIP_PERSIST_SETUP=0: built and
 // uploaded on every call (A/B runs); "log": one line per launch on stderr ("0log": both).  *built: this call built it (and
 // waited for the upload: the staging is on the stack).
@@ -48,12 +160,14 @@ static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
   const int n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;
   const int n_layer_roles = NL * (2 * W * H + NB);
   const int grid = std::max(1, std::min(s->ps_grid, n_layer_roles + n_tiles + 2 * W));
+  const char* deal_sw = sw::persist_deal();
+  const int policy = deal_sw && !strcmp(deal_sw, "legacy") ? PS_DEAL_LEGACY : PS_DEAL_SLACK;
   auto up = [](const void* p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); };
   const std::vector<uint64_t> key = {
       s->model_uid, (uint64_t)W, (uint64_t)S, (uint64_t)s->Lmax, (uint64_t)grid, (uint64_t)n_tiles, (uint64_t)n_pass,
       (uint64_t)s->enc_rows, (uint64_t)res_on, (uint64_t)m->ln_eps_inside_sqrt, up(s->state.p), up(s->x.p), up(s->P2.p),
       up(s->Pa.p), up(s->Pc.p), up(s->kc.p), up(s->vc.p), up(s->tabs.p), up(s->ckv.p), up(s->win_meta.p), up(s->ps_gx.p),
-      up(s->ps_gpa.p), up(s->ps_gpc.p), up(s->ps_gp2.p), up(s->ps_gxn.p)};
+      up(s->ps_gpa.p), up(s->ps_gpc.p), up(s->ps_gp2.p), up(s->ps_gxn.p), (uint64_t)policy};
   const char* sw_setup = sw::persist_setup();
   const bool cache_on = !(sw_setup && sw_setup[0] == '0');
   *built = !(cache_on && !s->ps_setup_key.empty() && s->ps_setup_key == key);
@@ -96,66 +210,11 @@ static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
     xi ^= 1;
   }
   // ---- one step's roles, dealt to the blocks: every block runs its own list, in dependency order, every step ----
-  std::vector<PsRole> lr;                            // the layer roles in dependency order
-  for (int l = 0; l < NL; l++) {
-    for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_ATTN, l, h, r});
-    for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_CROSS, l, h, r});
-    for (int j = 0; j < NB; j++) lr.push_back(PsRole{PSR_MLP, l, j, 0});
-  }
-  std::vector<std::vector<PsRole>> deal(grid);
-  for (size_t i = 0; i < lr.size(); i++) deal[i % grid].push_back(lr[i]);
-  // logits: blocks that hold a first-layer attention role stay free of it -- they are the first to be needed in the next
-  // step and should be back at their wait (weights requested) before this one ends.  Every logits block takes a run of
-  // consecutive 128-column tiles behind ONE fold + LayerNorm.
-  std::vector<int> cand;
-  for (int b = 0; b < grid; b++) {
-    bool early = false;
-    for (const PsRole& r : deal[b]) early |= r.layer == 0 && (r.kind == PSR_ATTN || r.kind == PSR_CROSS);
-    if (!early) cand.push_back(b);
-  }
-  if ((int)cand.size() * 4 < n_tiles) { cand.clear(); for (int b = 0; b < grid; b++) cand.push_back(b); }
-  // final LayerNorm (one per row): blocks without any layer role if there are some (they sit between the last MLP and
-  // the logits on the critical path), else the least loaded ones; they take no logits work
-  std::vector<char> is_fin(grid, 0);
-  {
-    std::vector<int> order(grid);
-    for (int b = 0; b < grid; b++) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
-    for (int r = 0; r < W; r++) { deal[order[r % grid]].push_back(PsRole{PSR_FINLN, 0, 0, r}); is_fin[order[r % grid]] = 1; }
-  }
-  if ((int)cand.size() > 2 * W) cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int b) { return is_fin[b] != 0; }), cand.end());
-  std::stable_sort(cand.begin(), cand.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
-  const int tpb = (n_tiles + (int)cand.size() - 1) / (int)cand.size();
-  const int n_lg = (n_tiles + tpb - 1) / tpb;
-  for (int q = 0; q < n_lg; q++)
-    deal[cand[q]].push_back(PsRole{PSR_LOGITS, q, q * tpb, std::min(tpb, n_tiles - q * tpb)});
-  // merge (one per row): the least loaded blocks
-  {
-    std::vector<int> order(grid);
-    for (int b = 0; b < grid; b++) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
-    for (int r = 0; r < W; r++) deal[order[r % grid]].push_back(PsRole{PSR_MERGE, 0, 0, r});
-  }
-  std::vector<PsRole> roles;
-  std::vector<int> role_off(grid + 1, 0);
-  for (int b = 0; b < grid; b++) {
-    role_off[b] = (int)roles.size();
-    roles.insert(roles.end(), deal[b].begin(), deal[b].end());
-  }
-  role_off[grid] = (int)roles.size();
-  // Resident operands (WHISPER_HIP_PERSIST_RESIDENT, default on; "0": off; "log": on, and one line on stderr): a block whose
-  // list holds exactly ONE layer role, a self- or cross-attention one, runs that role every step -- the kernel keeps what
-  // fits of the role's step-invariant operands in the LDS the roles leave free.  Blocks with several layer roles (a grid
-  // smaller than the layer roles) would have to share the region: they run as before.
-  std::vector<int> res_role(grid, -1);              // per block: the index of its resident role
-  int n_res = 0;
-  if (res_on)
-    for (int b = 0; b < grid; b++) {
-      int n_lr = 0, at = -1;
-      for (int i = role_off[b]; i < role_off[b + 1]; i++)
-        if (roles[i].kind <= PSR_MLP) { n_lr++; at = i; }
-      if (n_lr == 1 && roles[at].kind != PSR_MLP) { res_role[b] = at; n_res++; }
-    }
+  PsDeal deal = ps_deal_roles(NL, H, W, NB, n_tiles, grid, policy, res_on);
+  if (deal_sw && !strcmp(deal_sw, "log")) ps_deal_log(deal, grid);
+  std::vector<PsRole>& roles = deal.roles;
+  const std::vector<int>&role_off = deal.role_off, &res_role = deal.res_role;
+  const int n_lg = deal.n_lg, n_res = deal.n_res;
   WB_TRY(s->ps_layers.ensure(la.size() * sizeof(PsLayerArgs)));
   WB_TRY(s->ps_roles.ensure(roles.size() * sizeof(PsRole) + (role_off.size() + res_role.size()) * 4));
   WB_HIP(hipMemcpyAsync(s->ps_layers.p, la.data(), la.size() * sizeof(PsLayerArgs), hipMemcpyHostToDevice, st));
@@ -167,6 +226,7 @@ static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
   WB_HIP(hipStreamSynchronize(st));            // (the staging vectors above are on the stack)
   s->ps_pin_busy = false;
   s->ps_roles_host.swap(roles);
+  s->ps_role_off_host = role_off;
   s->ps_setup_grid = grid; s->ps_setup_n_lg = n_lg; s->ps_setup_n_res = n_res;
   s->ps_setup_key = key;
   return WB_OK;
@@ -297,6 +357,10 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
                    ((roles[i].kind == PSR_LOGITS ? 0 : roles[i].b) << 16);
       fwrite(kinds.data(), 4, kinds.size(), f);
       fwrite(hs.data(), 8, hs.size(), f);
+      // behind what older readers expect: a marker, then role_off (which block ran which role)
+      const int marker = 0x66664f52;                 // "ROff"
+      fwrite(&marker, 4, 1, f);
+      fwrite(s->ps_role_off_host.data(), 4, s->ps_role_off_host.size(), f);
       fclose(f);
     }
   }

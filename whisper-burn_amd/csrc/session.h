@@ -43,6 +43,7 @@ struct wb_session {
   // Same rule as wins_host / meta_host / mask_host: the key is voided before the contents change.
   std::vector<uint64_t> ps_setup_key;
   std::vector<wb::PsRole> ps_roles_host;        // the dealt roles (the stamps file names them)
+  std::vector<int> ps_role_off_host;            // ... and their blocks
   int ps_setup_grid = 0, ps_setup_n_lg = 0, ps_setup_n_res = 0;
   // pinned host words of a greedy call: [0, ps_pin_back) the control block's seed (host -> device), then what the host reads
   // after the launch (the error word, the control block, the token rows) behind ONE synchronisation

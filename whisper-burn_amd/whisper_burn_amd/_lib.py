@@ -157,6 +157,7 @@ SIGNATURES = {
     "wb_session_graph_count": (C.c_int, [C.c_void_p]),
     "wb_session_graph_captures": (C.c_int64, [C.c_void_p]),
     "wb_persist_resident_geometry": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_int32_p]),
+    "wb_persist_role_plan": (C.c_int, [C.c_int32] * 7 + [c_int32_p, c_int32_p, C.c_int32]),
     "wb_session_decode_sample": (C.c_int, [C.c_void_p, C.POINTER(WbDecodeParams), C.POINTER(WbSampleParams), c_int32_p,
                                            C.c_int32, c_uint8_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_double_p,
                                            c_int32_p]),
