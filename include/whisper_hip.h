@@ -563,6 +563,86 @@ int wb_sample_rows(int device, const float* logits, int32_t R, int32_t ld, int32
                    const int32_t* stream, const int32_t* position, int32_t eot, int32_t* out_token, float* out_logprob,
                    int32_t* out_err);
 
+/* ---- timestamp-token decoding: Whisper's timestamp rules on the device, segments (an extension) ----------------------
+ * Ids T = [tok_timestamp_begin, tok_timestamp_begin + n_timestamps) are timestamps (id tb + i stands for i *
+ * seconds_per_timestamp), N is every other id, end-of-text included.  gen = the tokens generated so far; the allowed set
+ * of the position being decided is everything not suppressed (wb_session_set_suppress) minus
+ *   (a) gen[-1] in T and (len(gen) < 2 or gen[-2] in T): all of T;
+ *   (b) gen[-1] in T and gen[-2] not in T: every id < tok_end_of_text outside T;
+ *   (c) with t the last generated timestamp: ids of T below t in case (b), below t + 1 otherwise;
+ *   (d) len(gen) == 0: all of N, and ids of T above tb + max_initial_timestamp_index (-1: no upper limit) -- when
+ *       n_timestamps > 0: a vocabulary without timestamps switches the rules off;
+ *   (e) ids of T above tb + max_timestamp_index (-1: none) -- for windows shorter than the timestamp range;
+ *   (f) with ts_lse = logsumexp over the allowed T and mN = max over the allowed N: if ts_lse > mN, all of N.
+ * The token is the argmax over what is left: by (logit descending, id ascending) at temperature 0, by the keys and
+ * counters of the sampling draw above at temperature > 0 (key (x - M) / T + g with M the row maximum over all ids).
+ * Recorded with it: x[token] - logsumexp(allowed).  The special mask (mask_until_len) is NOT applied in this mode:
+ * `suppress` takes its place.  (a) - (d) and (f) are Whisper's ApplyTimestampRules; (e) is this engine's. */
+typedef struct wb_timestamp_params {
+  int32_t tok_timestamp_begin;          /* <|0.00|> */
+  int32_t n_timestamps;                 /* 1501 in Whisper's vocabularies; 0: no id is a timestamp (the rules are off) */
+  int32_t max_initial_timestamp_index;  /* 50 (1.0 s); -1: no limit */
+  int32_t max_timestamp_index;          /* -1: none */
+  float seconds_per_timestamp;          /* 0.02 */
+  float temperature;                    /* 0: greedy; > 0: the Gumbel-max draw */
+  int32_t best_of;                      /* 1; > 1 needs temperature > 0 */
+  uint64_t seed;
+  int32_t attempt;
+} wb_timestamp_params;
+void wb_timestamp_params_default(wb_timestamp_params* p);   /* 0, 0, 50, -1, 0.02, 0, 1, 0, 0 */
+/* The static masks of timestamp decoding, u8 [n_vocab] each: suppress[v] != 0 removes id v at every step, suppress_first
+ * (may be NULL) additionally at the first generated position.  Kept on the device for the session's life. */
+int wb_session_set_suppress(wb_session* s, const uint8_t* suppress, const uint8_t* suppress_first);
+/* wb_session_decode_sample under the timestamp rules: best_of sequences per window from `prompt` (which must not pin
+ * <|notimestamps|>), on a fresh or rewound session; the rules, the pick and the row bookkeeping run on the device, chunks
+ * of steps replay as one graph -- the same graph for every temperature, seed and rule parameter.  active, stream_ids,
+ * out_tokens, out_lens, out_sum_logprob [W][best_of] (the f64 sum of the recorded log-probs) and out_best as there; the
+ * best-of pick (temperature > 0) is by sum_logprob / n_text.  p supplies max_depth and tok_end_of_text.  A row with a NaN
+ * logit or without an allowed id ends on end-of-text and the call fails with WB_ERR_STATE.
+ * Errors with nothing launched: those of wb_session_decode_sample, and temperature < 0 or not finite, temperature == 0 with
+ * best_of != 1, a timestamp range outside [0, n_vocab), end-of-text inside T -> WB_ERR_ARG; wb_session_set_suppress not
+ * called on this session -> WB_ERR_STATE (pass all-zero masks for none). */
+int wb_session_decode_timestamps(wb_session* s, const wb_decode_params* p, const wb_timestamp_params* tp,
+                                 const int32_t* prompt, int32_t prompt_len, const uint8_t* active, const int32_t* stream_ids,
+                                 int32_t* out_tokens, int32_t row_stride, int32_t* out_lens, double* out_sum_logprob,
+                                 int32_t* out_best);
+/* Test hook: the rules + pick alone (the device function of the chain kernel) on caller data in host memory.  logits
+ * [R][ld] (ld >= V); suppress / suppress_first u8 [V] (NULL: none); per row the state of the rules: n_gen = len(gen),
+ * prev1 / prev2 = gen[-1] / gen[-2] (read when n_gen >= 1 / 2), last_ts = the last generated timestamp id or -1; stream /
+ * position [R] as wb_sample_rows.  out_token / out_logprob / out_forced [R] (forced: rule (f) removed N), out_stats [R][2]
+ * = (ts_lse, mN).  A row with a NaN logit or without an allowed id gives eot, log-prob 0 and *out_err = 1.  `device` only
+ * hosts the buffers. */
+int wb_timestamp_rows(int device, const float* logits, int32_t R, int32_t ld, int32_t V, const uint8_t* suppress,
+                      const uint8_t* suppress_first, int32_t tok_timestamp_begin, int32_t n_timestamps,
+                      int32_t max_initial_timestamp_index, int32_t max_timestamp_index, float temperature, uint64_t seed,
+                      int32_t attempt, const int32_t* n_gen, const int32_t* prev1, const int32_t* prev2,
+                      const int32_t* last_ts, const int32_t* stream, const int32_t* position, int32_t eot,
+                      int32_t* out_token, float* out_logprob, int32_t* out_forced, float* out_stats, int32_t* out_err);
+/* Whisper transcribe()'s slicing of one window's generated tokens (host only).  tokens [n]: the generated tokens (no
+ * prompt); everything from the first end-of-text on is ignored.  Every pair of consecutive timestamps closes a segment; a
+ * row that ends on a single timestamp closes a last segment there; a row without a pair is one segment from 0 to its last
+ * timestamp (if that is not <|0.00|>) or to the window end.  window_index: the window's length in timestamp units.
+ * Per segment: seg_begin / seg_end = its token index range [begin, end) (timestamps included), seg_start / seg_end_time in
+ * seconds relative to the window.  *advance_index: the timestamp index by which the window moves on -- the last closing
+ * timestamp, or window_index when the row ends on a single timestamp or has no pair.  cap: capacity of the four arrays
+ * (n + 1 always suffices); WB_ERR_ARG when it is too small. */
+int wb_segments_from_tokens(const int32_t* tokens, int32_t n, int32_t tok_timestamp_begin, int32_t n_timestamps,
+                            int32_t tok_end_of_text, int32_t window_index, float seconds_per_timestamp, int32_t* seg_begin,
+                            int32_t* seg_end, float* seg_start, float* seg_end_time, int32_t cap, int32_t* n_segments,
+                            int32_t* advance_index);
+/* Long-form transcription by timestamps: the window at `seek` (at most the model's window length) is decoded by
+ * wb_session_decode_timestamps from `prompt` (max_timestamp_index clamped to the window's length), sliced by
+ * wb_segments_from_tokens, and seek advances by advance_index * seconds_per_timestamp * sample_rate samples -- a whole
+ * window when that is 0, so the loop always ends.  Windows are sequential, one at a time.  Outputs: flat segment arrays
+ * (seg_start / seg_end_time in seconds of the waveform; seg_tok_begin / seg_tok_end index `text_tokens`), the concatenated
+ * non-timestamp tokens of all segments (end-of-text dropped) in text_tokens, and the number of windows decoded.  WB_ERR_ARG
+ * when seg_cap or text_cap is too small. */
+int wb_waveform_to_segments(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                            const wb_timestamp_params* tp, const uint8_t* suppress, const uint8_t* suppress_first,
+                            const int32_t* prompt, int32_t prompt_len, float* seg_start, float* seg_end_time,
+                            int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap, int32_t* n_segments,
+                            int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens, int32_t* n_windows);
+
 /* The reference's retired greedy decoder kept its repetition detectors (transcribe.rs:385-447, dead code there):
  *   wb_first_repetition_end        :385-393   (period > n, a usize underflow panic there -> WB_ERR_ARG)
  *   wb_repetition_period           :395-417   returns the period, 0 for None

@@ -72,6 +72,20 @@ pub struct wb_fallback_params {
     pub tok_no_speech: i32,
 }
 
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct wb_timestamp_params {
+    pub tok_timestamp_begin: i32,
+    pub n_timestamps: i32,
+    pub max_initial_timestamp_index: i32,
+    pub max_timestamp_index: i32,
+    pub seconds_per_timestamp: c_float,
+    pub temperature: c_float,
+    pub best_of: i32,
+    pub seed: u64,
+    pub attempt: i32,
+}
+
 /// Compression ratio of one window's generated tokens, computed on the caller's side (it owns the tokenizer).
 pub type wb_ratio_fn = Option<unsafe extern "C" fn(user: *mut c_void, tokens: *const i32, n: i32) -> c_double>;
 
@@ -164,6 +178,20 @@ extern "C" {
                           row_masked: *const u8, row_stats: *const c_float, temperature: c_float, seed: u64, attempt: i32,
                           stream: *const i32, position: *const i32, eot: i32, out_token: *mut i32,
                           out_logprob: *mut c_float, out_err: *mut i32) -> c_int;
+    // timestamp-token decoding: Whisper's timestamp rules on the device, segments (no counterpart in the reference)
+    pub fn wb_session_set_suppress(s: *mut wb_session, suppress: *const u8, suppress_first: *const u8) -> c_int;
+    pub fn wb_timestamp_rows(device: c_int, logits: *const c_float, R: i32, ld: i32, V: i32, suppress: *const u8,
+                             suppress_first: *const u8, tok_timestamp_begin: i32, n_timestamps: i32,
+                             max_initial_timestamp_index: i32, max_timestamp_index: i32, temperature: c_float, seed: u64,
+                             attempt: i32, n_gen: *const i32, prev1: *const i32, prev2: *const i32, last_ts: *const i32,
+                             stream: *const i32, position: *const i32, eot: i32, out_token: *mut i32,
+                             out_logprob: *mut c_float, out_forced: *mut i32, out_stats: *mut c_float,
+                             out_err: *mut i32) -> c_int;
+    pub fn wb_segments_from_tokens(tokens: *const i32, n: i32, tok_timestamp_begin: i32, n_timestamps: i32,
+                                   tok_end_of_text: i32, window_index: i32, seconds_per_timestamp: c_float,
+                                   seg_begin: *mut i32, seg_end: *mut i32, seg_start: *mut c_float,
+                                   seg_end_time: *mut c_float, cap: i32, n_segments: *mut i32,
+                                   advance_index: *mut i32) -> c_int;
     pub fn wb_session_begin(m: *mut wb_model, pcm: *const c_float, n_pcm: i64, starts: *const i64, lens: *const i64,
                             n_windows: c_int, max_beams: c_int, padding: c_int, out: *mut *mut wb_session) -> c_int;
     pub fn wb_session_set_special_mask(s: *mut wb_session, is_special: *const u8) -> c_int;
@@ -191,7 +219,7 @@ extern "C" {
     pub fn wb_version() -> *const c_char;
 }
 
-// Temperature sampling and the decode fallback: the entry points whose arguments are the parameter structs / the callback
+// Temperature sampling, the decode fallback and timestamp decoding: the entry points whose arguments are the parameter structs / the callback
 // type defined above (their own block: tests/test_rust_shim.py type-checks the first block against the header's scalars).
 extern "C" {
     pub fn wb_sample_params_default(p: *mut wb_sample_params);
@@ -199,6 +227,17 @@ extern "C" {
                                     prompt: *const i32, prompt_len: i32, active: *const u8, stream_ids: *const i32,
                                     out_tokens: *mut i32, row_stride: i32, out_lens: *mut i32,
                                     out_sum_logprob: *mut c_double, out_best: *mut i32) -> c_int;
+    pub fn wb_timestamp_params_default(p: *mut wb_timestamp_params);
+    pub fn wb_session_decode_timestamps(s: *mut wb_session, p: *const wb_decode_params, tp: *const wb_timestamp_params,
+                                        prompt: *const i32, prompt_len: i32, active: *const u8, stream_ids: *const i32,
+                                        out_tokens: *mut i32, row_stride: i32, out_lens: *mut i32,
+                                        out_sum_logprob: *mut c_double, out_best: *mut i32) -> c_int;
+    pub fn wb_waveform_to_segments(m: *mut wb_model, pcm: *const c_float, n: i64, sample_rate: c_int,
+                                   p: *const wb_decode_params, tp: *const wb_timestamp_params, suppress: *const u8,
+                                   suppress_first: *const u8, prompt: *const i32, prompt_len: i32,
+                                   seg_start: *mut c_float, seg_end_time: *mut c_float, seg_tok_begin: *mut i32,
+                                   seg_tok_end: *mut i32, seg_cap: i32, n_segments: *mut i32, text_tokens: *mut i32,
+                                   text_cap: i64, n_text_tokens: *mut i64, n_windows: *mut i32) -> c_int;
     pub fn wb_fallback_params_default(p: *mut wb_fallback_params);
     pub fn wb_fallback_decide(fp: *const wb_fallback_params, avg_logprob: c_float, no_speech_prob: c_float,
                               ratio: c_float) -> c_int;

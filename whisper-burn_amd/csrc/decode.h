@@ -218,6 +218,63 @@ struct SampleRowsArgs {
 };
 void launch_sample_rows(hipStream_t st, const SampleRowsArgs& a);
 
+// ---- device-chained timestamp decoding (tsrules.hip, ts_chain.cpp) ------------------------------------------------
+// The sampling chain's rows and launch shape under Whisper's timestamp rules: the bookkeeping kernel behind the logits tail
+// filters the row by the rules (per-row state words + the static suppress bytes, no mask array), picks the token (argmax at
+// 1 / T = 0, the Gumbel-max draw of sample.hip otherwise), records it with its log-prob under the filters and prepares the
+// next step.  Every rule parameter, 1 / T, seed, attempt and the streams live in the control block: one captured graph serves
+// every temperature, seed and rule setting.
+enum { TC_NDONE = 0, TC_ALLDONE = 1, TC_ERR = 2, TC_NROWS = 3, TC_BEST_OF = 4, TC_ATTEMPT = 5, TC_SEED_LO = 6, TC_SEED_HI = 7,
+       TC_INVT = 8,           // the bits of the f32 1 / T; 0: greedy (the key is the logit itself)
+       TC_TB = 9, TC_NTS = 10, TC_MAX_INIT = 11, TC_MAX_TS = 12, TC_HDR = 16 };
+struct TsChainLayout {
+  int S = 0, W = 0, max_depth = 0;
+  // int offsets: stream / fin / ngen / last_was_ts / penult_was_ts / last_ts [S], win_fin [W]; then doubles sum [S] (8-byte
+  // aligned); then the generated tokens int[S][max_depth]
+  int stream = 0, fin = 0, ngen = 0, last_was = 0, penult_was = 0, last_ts = 0, win_fin = 0, sum = 0, tokens = 0, total_ints = 0;
+};
+inline TsChainLayout make_ts_layout(int S, int W, int max_depth) {
+  TsChainLayout b;
+  b.S = S; b.W = W; b.max_depth = max_depth;
+  b.stream = TC_HDR; b.fin = b.stream + S; b.ngen = b.fin + S; b.last_was = b.ngen + S; b.penult_was = b.last_was + S;
+  b.last_ts = b.penult_was + S; b.win_fin = b.last_ts + S;
+  b.sum = (b.win_fin + W + 1) & ~1;
+  b.tokens = b.sum + 2 * S;
+  b.total_ints = b.tokens + S * max_depth;
+  return b;
+}
+// The rule state of one row (block-uniform): what the filter of a position needs beside the suppress bytes.
+struct TsRowState {
+  int n_gen = 0;                // tokens generated so far
+  int last_was = 0, penult_was = 0;   // gen[-1] / gen[-2] is a timestamp (penult_was is read only when n_gen >= 2)
+  int last_ts = -1;             // the last generated timestamp id, -1: none
+};
+struct TsRules { int tb = 0, n_ts = 0, max_init = -1, max_ts = -1, eot = 0; };
+struct TsChainArgs {
+  int* ctl = nullptr; TsChainLayout tl;
+  const float* logits = nullptr; int V = 0;                            // the step's unmasked logits [S][V]
+  const uint32_t* sup = nullptr; const uint32_t* sup_first = nullptr;  // suppress bytes [V] packed 4 per word (pad bytes 0);
+                                                                       // sup_first = suppress | suppress_first; null: none
+  const float* row_stats = nullptr;                                    // [S][2]: [0] the row maximum over all ids (the key's shift)
+  int* state = nullptr; StepLayout lay;
+  int eot = 0;
+  int* tabs = nullptr; int Lmax = 0; const float* E = nullptr; const float* pos = nullptr; int d = 0; float* x = nullptr;
+};
+void launch_dec_ts_update(hipStream_t st, const TsChainArgs& a, int n_rows);
+// test hook (wb_timestamp_rows): the filter + pick alone, one block per row, on caller data in device memory
+struct TsRowsArgs {
+  const float* logits = nullptr; int R = 0, ld = 0, V = 0;
+  const uint32_t* sup = nullptr; const uint32_t* sup_first = nullptr;
+  const float* row_max = nullptr;                                      // [R]: the row maximum over all ids
+  TsRules rules;
+  float inv_t = 0.f; uint32_t seed_lo = 0, seed_hi = 0, attempt = 0;
+  const int32_t* n_gen = nullptr; const int32_t* prev1 = nullptr; const int32_t* prev2 = nullptr; const int32_t* last_ts = nullptr;
+  const int32_t* stream = nullptr; const int32_t* position = nullptr;  // [R]
+  int32_t* out_token = nullptr; float* out_logprob = nullptr; int32_t* out_forced = nullptr; float* out_stats = nullptr;
+  int32_t* out_err = nullptr;                                          // [R], [R], [R], [R][2], one word
+};
+void launch_ts_rows(hipStream_t st, const TsRowsArgs& a);
+
 // ---- fused small-batch sublayer kernels (decode_fused.hip) ----------------------------------------------
 // Common prologue of both: x = x_in + (pbias + sum_s pend[s]) (KSp planes of [S][d]; KSp = 0: none), block 0
 // writes x to x_out, then LayerNorm(ln_g, ln_b, ln_eps).

@@ -328,8 +328,9 @@ static int enqueue_logits_tail(StepCtx& c, bool timed, bool merge_prepares, int*
   const StepLayout& L = s->lay;
   const BeamStepIO* bio = call.bio;
   const SampleStepIO* sio = call.sio;
-  int32_t* out_id_dev = bio ? bio->topk_id : sio ? sio->topk_id : reinterpret_cast<int32_t*>(s->host_block_dev + (size_t)L.total * 4);
-  float* out_lp_dev = bio ? bio->topk_lp : sio ? sio->topk_lp
+  const TsStepIO* tio = call.tio;
+  int32_t* out_id_dev = bio ? bio->topk_id : sio ? sio->topk_id : tio ? tio->topk_id : reinterpret_cast<int32_t*>(s->host_block_dev + (size_t)L.total * 4);
+  float* out_lp_dev = bio ? bio->topk_lp : sio ? sio->topk_lp : tio ? tio->topk_lp
                           : reinterpret_cast<float*>(s->host_block_dev + (size_t)L.total * 4 + (size_t)S * TOPK_MAX * 4);
   const float* pend = s->P2.as<float>(); const float* pbias = m->dec[c.NL - 1].mlp2.b;   // what the last layer left pending
   if (!p.fuse_ln) c.resolve(pend, p.k2, pbias, m->ln_dec);
@@ -369,6 +370,10 @@ static int enqueue_logits_tail(StepCtx& c, bool timed, bool merge_prepares, int*
     prof_tag(KC_SAMPLE_UPDATE, (call.use_mask ? 8.0 : 4.0) * (double)n * V);
     launch_dec_sample_update(st, u, n);
   }
+  if (tio) {   // the rules read the row's logits and its suppress bytes once
+    prof_tag(KC_TS_UPDATE, 5.0 * (double)n * V);
+    launch_dec_ts_update(st, tio->upd, n);
+  }
   if (timed && tm_logits.on) {
     WB_HIP(hipStreamSynchronize(st));
     tm_logits.collect();
@@ -391,7 +396,7 @@ static int enqueue_step(wb_session* s, const StepPlan& p, const StepCall& call, 
   // first step is prepared by session_greedy_chain)
   const bool merge_prepares = call.chained && p.fuse_ln;
   // (device-chained beam search / sampling: the bookkeeping launch behind the previous step prepared this one)
-  if (!merge_prepares && !bio && !call.sio) {
+  if (!merge_prepares && !bio && !call.sio && !call.tio) {
     prof_tag(KC_PREPARE, 8.0 * c.n * c.d);
     launch_dec_prepare(c.st, hst, s->state.as<int>(), s->lay, c.n, c.tabs, s->Lmax, s->m->tok_emb, s->m->dec_pos, c.d, c.xb[0], gctl);
   }
@@ -407,7 +412,7 @@ int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call) {
   if (!plan.use_graph) {
     for (int i = 0; i < reps; i++) {
       WB_TRY(enqueue_step(s, plan, call, true));
-      if (call.chained || call.bio || call.sio) s->prof_step_off++;
+      if (call.chained || call.bio || call.sio || call.tio) s->prof_step_off++;
     }
     return WB_OK;
   }
@@ -433,8 +438,10 @@ int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call) {
   // first step's position via the control block layout: session_beam_chain drops the graphs when those change)
   // (the rest of the plan follows from n_launch, fuse_ln and what the signature above carries: the model, S, W, max_beams,
   // n_chunks, maxC -- and the process's switches)
-  // (a sampling-chain graph bakes in its control block and max_depth: session_sample_chain drops ITS graphs when those change)
+  // (a sampling-chain graph bakes in its control block and max_depth: session_sample_chain drops ITS graphs when those change;
+  // a timestamp-chain graph likewise, and its suppress buffers: session_ts_chain)
   const uint64_t key = ((uint64_t)reps << 48) | ((uint64_t)plan.n_launch << 32) | ((uint64_t)call.k << 8) | (call.sio ? GRAPH_KEY_SAMPLE : 0u) |
+                       (call.tio ? GRAPH_KEY_TS : 0u) |
                        (call.bio ? 8u : 0u) | (call.chained ? 4u : 0u) | ((uint64_t)call.use_mask << 1) | (plan.fuse_ln ? 1u : 0u);
   auto it = s->graphs.find(key);
   if (it == s->graphs.end()) {

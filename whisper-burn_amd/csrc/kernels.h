@@ -22,6 +22,8 @@ enum KernelClass {
   KC_SCORE_LOGITS, KC_SCORE_MERGE,
   // temperature sampling (sample.hip): the draw + bookkeeping launch behind a sampling step's logits tail
   KC_SAMPLE_UPDATE,
+  // timestamp decoding (tsrules.hip): the filter + pick + bookkeeping launch behind a timestamp step's logits tail
+  KC_TS_UPDATE,
   KC_COUNT
 };
 void prof_tag(int cls, double algo_bytes);

@@ -34,7 +34,8 @@ static const char* const g_kernel_names[KC_COUNT] = {
     "dec_beam_update (beam.rs bookkeeping on the device)", "dec_fold_ln_rows (final fold + LayerNorm, 9 - 16 rows)",
     "align_row_stats (cross-attention score max / sum)", "align_accumulate (weights + z-score + median + head mean)",
     "align_dtw (anti-diagonal DTW + backtrace)", "score_logits (LN rows x E^T -> per-split max / sum, target, probes)",
-    "score_merge (splits -> lse, log-probs)", "dec_sample_update (Gumbel-max draw + row bookkeeping)"};
+    "score_merge (splits -> lse, log-probs)", "dec_sample_update (Gumbel-max draw + row bookkeeping)",
+    "dec_ts_update (timestamp rules + pick + row bookkeeping)"};
 struct PendingLaunch { hipEvent_t a, b; int cls; double bytes; };
 static std::mutex g_prof_mu;
 static std::vector<PendingLaunch> g_pending;

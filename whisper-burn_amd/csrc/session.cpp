@@ -83,6 +83,7 @@ int session_create(wb_model* m, int n_windows, int max_beams, int padding, wb_se
   s->has_mask = false; s->decode_ready = false; s->last_had_logits = 0; s->last_use_mask = 0;
   s->sample_rate = 16000.0;          // per-use state: a pooled session must not remember its previous caller
   s->smp_best_of = 0; s->smp_depth = 0; s->smp_len.clear(); s->smp_tokens.clear();
+  s->has_suppress = false;
   *out = s;
   return WB_OK;
 }

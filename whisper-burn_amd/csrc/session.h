@@ -57,6 +57,12 @@ struct wb_session {
   // every sample of the last sampling call (wb_session_last_samples): generated tokens [W][best_of][depth], their counts
   // [W][best_of] (-1: the window was not active)
   std::vector<int32_t> smp_tokens, smp_len; int smp_best_of = 0, smp_depth = 0;
+  // device-chained timestamp decoding (decode.h: TsChainArgs): control block, the steps' top-1 rows, and the suppress bytes
+  // [2][ceil(V / 4)] words -- suppress, then suppress | suppress_first (wb_session_set_suppress; has_suppress: set on this use)
+  wb::DevMem ts_ctl, ts_topk, ts_sup;
+  std::vector<uint8_t> ts_sup_host; void* ts_sup_dev_ptr = nullptr;     // what ts_sup holds (same rule as mask_host)
+  bool has_suppress = false;
+  uint64_t ts_sig = 0;          // what the captured timestamp steps bake in (session_ts_chain)
   std::vector<int> prev_len, prev_win;
   int prev_n = 0, step = 0;
   bool has_mask = false, decode_ready = false;
@@ -119,6 +125,11 @@ struct SampleCall { float temperature; int best_of; uint64_t seed; int attempt; 
 int session_sample_chain(wb_session* s, const int32_t* prompt, int prompt_len, const SampleCall& sp, const uint8_t* active,
                          const int32_t* stream_ids, int eot, int max_depth, int mask_until_len, int32_t* out_tokens,
                          int32_t row_stride, int32_t* out_lens, double* out_sum, int32_t* out_best);
+// timestamp-token decoding with the rules, the pick and the bookkeeping on the device (ts_chain.cpp); active / stream_ids /
+// out_sum / out_best may be null
+int session_ts_chain(wb_session* s, const wb_timestamp_params& tp, const int32_t* prompt, int prompt_len, const uint8_t* active,
+                     const int32_t* stream_ids, int eot, int max_depth, int32_t* out_tokens, int32_t row_stride,
+                     int32_t* out_lens, double* out_sum, int32_t* out_best);
 int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_depth, int mask_until_len, int prompt_len,
                          int32_t* out_tokens, int32_t row_stride, int32_t* out_lens);
 // wb_session_align (align.cpp); drop_last_rows non-null: drop_last per window instead of the scalar, and a row that leaves

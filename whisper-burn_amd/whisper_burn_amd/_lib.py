@@ -42,6 +42,12 @@ class WbFallbackParams(C.Structure):
                 ("compression_ratio_threshold", C.c_float), ("seed", C.c_uint64), ("tok_no_speech", C.c_int32)]
 
 
+class WbTimestampParams(C.Structure):
+    _fields_ = [("tok_timestamp_begin", C.c_int32), ("n_timestamps", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
+                ("max_timestamp_index", C.c_int32), ("seconds_per_timestamp", C.c_float), ("temperature", C.c_float),
+                ("best_of", C.c_int32), ("seed", C.c_uint64), ("attempt", C.c_int32)]
+
+
 # wb_ratio_fn (include/whisper_hip.h)
 RATIO_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, c_int32_p, C.c_int32)
 
@@ -172,6 +178,21 @@ SIGNATURES = {
     "wb_sample_rows": (C.c_int, [C.c_int, c_float_p, C.c_int32, C.c_int32, C.c_int32, c_float_p, c_uint8_p, c_float_p,
                                  C.c_float, C.c_uint64, C.c_int32, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_float_p,
                                  c_int32_p]),
+    "wb_timestamp_params_default": (None, [C.POINTER(WbTimestampParams)]),
+    "wb_session_set_suppress": (C.c_int, [C.c_void_p, c_uint8_p, c_uint8_p]),
+    "wb_session_decode_timestamps": (C.c_int, [C.c_void_p, C.POINTER(WbDecodeParams), C.POINTER(WbTimestampParams), c_int32_p,
+                                               C.c_int32, c_uint8_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_double_p,
+                                               c_int32_p]),
+    "wb_timestamp_rows": (C.c_int, [C.c_int, c_float_p, C.c_int32, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_int32, c_int32_p, c_int32_p,
+                                    c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_float_p, c_int32_p,
+                                    c_float_p, c_int32_p]),
+    "wb_segments_from_tokens": (C.c_int, [c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                          c_int32_p, c_int32_p, c_float_p, c_float_p, C.c_int32, c_int32_p, c_int32_p]),
+    "wb_waveform_to_segments": (C.c_int, [C.c_void_p, c_float_p, C.c_int64, C.c_int, C.POINTER(WbDecodeParams),
+                                          C.POINTER(WbTimestampParams), c_uint8_p, c_uint8_p, c_int32_p, C.c_int32, c_float_p,
+                                          c_float_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p, C.c_int64,
+                                          c_int64_p, c_int32_p]),
     "wb_first_repetition_end": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_repetition_period": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_find_repeated_tokens_index": (C.c_int, [c_int32_p, C.c_int64, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),
@@ -193,8 +214,8 @@ class WbKernelStat(C.Structure):
 def profile_kernels(reset: bool = True):
     """wb_profile_kernels as a list of dicts (name, calls, total_ms, algo_bytes)."""
     lib = load()
-    buf = (WbKernelStat * 32)()
-    n = min(32, int(lib.wb_profile_kernels(C.cast(buf, C.c_void_p), 32, int(reset))))
+    buf = (WbKernelStat * 48)()
+    n = min(48, int(lib.wb_profile_kernels(C.cast(buf, C.c_void_p), 48, int(reset))))
     return [dict(name=buf[i].name.decode(), calls=int(buf[i].calls), total_ms=float(buf[i].total_ms),
                  algo_bytes=float(buf[i].algo_bytes)) for i in range(n)]
 

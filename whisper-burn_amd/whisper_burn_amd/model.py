@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import WbDecodeParams, WbDims, WbError, WbFallbackParams, WbSampleParams, check
+from ._lib import WbDecodeParams, WbDims, WbError, WbFallbackParams, WbSampleParams, WbTimestampParams, check
 from .tokens import SpecialTokens
 
 WB_F32, WB_BF16 = 0, 1
@@ -126,6 +126,97 @@ def SampleParams(temperature: float = 1.0, best_of: int = 5, seed: int = 0, atte
     _lib.load().wb_sample_params_default(C.byref(p))
     p.temperature, p.best_of, p.seed, p.attempt = temperature, best_of, seed, attempt
     return p
+
+
+def TimestampParams(timestamp_begin: int = 0, n_timestamps: int = 0, max_initial_timestamp_index: int = 50,
+                    max_timestamp_index: int = -1, seconds_per_timestamp: float = 0.02, temperature: float = 0.0,
+                    best_of: int = 1, seed: int = 0, attempt: int = 0) -> WbTimestampParams:
+    """wb_timestamp_params: the timestamp range [timestamp_begin, timestamp_begin + n_timestamps), the two index limits (-1:
+    none) and the pick (temperature 0: greedy; > 0: the sampling draw, best of `best_of`)."""
+    p = WbTimestampParams()
+    _lib.load().wb_timestamp_params_default(C.byref(p))
+    p.tok_timestamp_begin, p.n_timestamps = int(timestamp_begin), int(n_timestamps)
+    p.max_initial_timestamp_index, p.max_timestamp_index = int(max_initial_timestamp_index), int(max_timestamp_index)
+    p.seconds_per_timestamp, p.temperature, p.best_of, p.seed, p.attempt = seconds_per_timestamp, temperature, best_of, seed, attempt
+    return p
+
+
+def _u8v(a, V: int) -> Optional[np.ndarray]:
+    if a is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)
+    assert a.shape == (V,), (a.shape, V)
+    return a
+
+
+def timestamp_rows(logits, tp: WbTimestampParams, n_gen, prev1, prev2, last_ts, stream, position, eot: int,
+                   V: Optional[int] = None, suppress=None, suppress_first=None, device: int = 0):
+    """The timestamp rules + pick alone (wb_timestamp_rows, a test hook): logits [R, ld] of which the first V columns are the
+    row; per row n_gen = len(gen), prev1 / prev2 = gen[-1] / gen[-2], last_ts = the last generated timestamp or -1.
+    Returns (token [R], logprob [R], forced [R], stats [R, 2] = (ts_lse, mN), error word)."""
+    x = _f32(logits)
+    R, ld = x.shape
+    V = ld if V is None else V
+    cols = [_i32(c) for c in (n_gen, prev1, prev2, last_ts, stream, position)]
+    assert all(c.shape == (R,) for c in cols)
+    sup, sup1 = _u8v(suppress, V), _u8v(suppress_first, V)
+    tok = np.full(R, -1, dtype=np.int32)
+    lp = np.full(R, np.nan, dtype=np.float32)
+    forced = np.full(R, -1, dtype=np.int32)
+    stats = np.full((R, 2), np.nan, dtype=np.float32)
+    err = np.full(1, -1, dtype=np.int32)
+    check(_lib.load().wb_timestamp_rows(device, _fp(x), R, ld, V, _u8p(sup), _u8p(sup1), tp.tok_timestamp_begin, tp.n_timestamps,
+                                        tp.max_initial_timestamp_index, tp.max_timestamp_index, float(tp.temperature),
+                                        int(tp.seed), int(tp.attempt), *[_ip(c) for c in cols], int(eot), _ip(tok), _fp(lp),
+                                        _ip(forced), _fp(stats), _ip(err)))
+    return tok, lp, forced, stats, int(err[0])
+
+
+def segments_from_tokens(tokens, tp: WbTimestampParams, eot: int, window_index: int):
+    """Whisper transcribe()'s slicing of one window's generated tokens (wb_segments_from_tokens, host only): a list of
+    dict(begin, end, start, end_time) -- token index range and seconds relative to the window -- and the advance index."""
+    t = _i32(list(tokens))
+    cap = len(t) + 1
+    sb, se = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    t0, t1 = np.zeros(cap, dtype=np.float32), np.zeros(cap, dtype=np.float32)
+    k, adv = C.c_int32(0), C.c_int32(0)
+    check(_lib.load().wb_segments_from_tokens(_ip(t) if len(t) else None, len(t), tp.tok_timestamp_begin, tp.n_timestamps, int(eot),
+                                              int(window_index), float(tp.seconds_per_timestamp), _ip(sb), _ip(se), _fp(t0),
+                                              _fp(t1), cap, C.byref(k), C.byref(adv)))
+    return [dict(begin=int(sb[i]), end=int(se[i]), start=float(t0[i]), end_time=float(t1[i])) for i in range(k.value)], int(adv.value)
+
+
+def waveform_to_segments(whisper: "Whisper", st: SpecialTokens, waveform, sample_rate: int = 16000, params=None,
+                         timestamps: Optional[WbTimestampParams] = None, suppress=None, suppress_first=None, prompt=None):
+    """Long-form transcription by timestamps (wb_waveform_to_segments): the window moves by the last decoded timestamp.
+    Returns (segments, tokens, n_windows): segments = dict(start, end, tokens) with absolute seconds and the segment's
+    non-timestamp tokens; tokens = their concatenation."""
+    from .tokens import default_suppress
+    wav = _f32(waveform).reshape(-1)
+    p = params if params is not None else decode_params(st)
+    tp = timestamps if timestamps is not None else TimestampParams(st.timestamp_begin, st.n_timestamps)
+    V = whisper.dims["n_vocab"]
+    if suppress is None:
+        suppress, d1 = default_suppress(st)
+        suppress_first = d1 if suppress_first is None else suppress_first
+    sup, sup1 = _u8v(suppress, V), _u8v(suppress_first, V)
+    pr = _i32([st.start_of_transcript, st.language, st.transcribe] if prompt is None else list(prompt))
+    wlen = max_waveform_samples(whisper.max_mel_frames() - p.padding)
+    # (capacity: a window advances by at least one timestamp unit -- or wholly -- and a tail below 400 samples is not decoded)
+    spts = max(1, int(tp.seconds_per_timestamp * sample_rate))
+    n_win_max = max(len(wav) // 400, len(wav) // spts) + 2
+    seg_cap = n_win_max * (p.max_depth + 1)
+    text_cap = n_win_max * max(p.max_depth, 1)
+    t0, t1 = np.zeros(seg_cap, dtype=np.float32), np.zeros(seg_cap, dtype=np.float32)
+    b, e = np.zeros(seg_cap, dtype=np.int32), np.zeros(seg_cap, dtype=np.int32)
+    text = np.zeros(text_cap, dtype=np.int32)
+    ns, nw, nt = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(_lib.load().wb_waveform_to_segments(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p), C.byref(tp), _u8p(sup),
+                                              _u8p(sup1), _ip(pr), len(pr), _fp(t0), _fp(t1), _ip(b), _ip(e), seg_cap,
+                                              C.byref(ns), _ip(text), text_cap, C.byref(nt), C.byref(nw)))
+    toks = text[:nt.value].tolist()
+    segs = [dict(start=float(t0[i]), end=float(t1[i]), tokens=toks[b[i]:e[i]]) for i in range(ns.value)]
+    return segs, toks, int(nw.value)
 
 
 def FallbackParams(temperatures=None, best_of: Optional[int] = None, logprob_threshold: Optional[float] = -1.0,
@@ -830,6 +921,31 @@ class Session:
         check(_lib.load().wb_session_decode_sample(self._h, C.byref(params), C.byref(sample), _ip(pr), len(pr), _u8p(act),
                                                    _ip(sid) if sid is not None else None, _ip(toks), toks.shape[1], _ip(lens),
                                                    sums.ctypes.data_as(_lib.c_double_p), _ip(best)))
+        return [toks[i, :lens[i]].tolist() for i in range(W)], sums, best
+
+    def set_suppress(self, suppress, suppress_first=None) -> None:
+        """The static masks of timestamp decoding (wb_session_set_suppress): [V] of 0 / 1 each."""
+        V = self._w.dims["n_vocab"]
+        check(_lib.load().wb_session_set_suppress(self._h, _u8p(_u8v(suppress, V)), _u8p(_u8v(suppress_first, V))))
+
+    def decode_timestamps(self, params: WbDecodeParams, timestamps: WbTimestampParams, prompt=None, active=None,
+                          stream_ids=None, out_tokens: Optional[np.ndarray] = None, out_lens: Optional[np.ndarray] = None):
+        """Decoding under the timestamp rules (wb_session_decode_timestamps), on a fresh or rewound session after
+        set_suppress.  prompt: default [sot, language, transcribe] of `params`; the other arguments and the result as
+        decode_sample: (rows, sum_logprob [W, best_of] f64, best [W])."""
+        W, bo = self.n_windows, int(timestamps.best_of)
+        pr = _i32([params.tok_start_of_transcript, params.tok_language, params.tok_transcribe] if prompt is None else list(prompt))
+        stride = len(pr) + params.max_depth + 4
+        toks = out_tokens if out_tokens is not None else np.zeros((W, stride), dtype=np.int32)
+        lens = out_lens if out_lens is not None else np.zeros(W, dtype=np.int32)
+        assert toks.dtype == np.int32 and toks.flags.c_contiguous and toks.shape[0] == W and lens.dtype == np.int32
+        act = np.ascontiguousarray(active, dtype=np.uint8) if active is not None else None
+        sid = _i32(stream_ids) if stream_ids is not None else None
+        sums = np.full((W, max(bo, 1)), np.nan, dtype=np.float64)
+        best = np.full(W, -1, dtype=np.int32)
+        check(_lib.load().wb_session_decode_timestamps(self._h, C.byref(params), C.byref(timestamps), _ip(pr), len(pr), _u8p(act),
+                                                       _ip(sid) if sid is not None else None, _ip(toks), toks.shape[1],
+                                                       _ip(lens), sums.ctypes.data_as(_lib.c_double_p), _ip(best)))
         return [toks[i, :lens[i]].tolist() for i in range(W)], sums, best
 
     def last_samples(self, best_of: int, max_depth: int) -> List[List[Optional[List[int]]]]:

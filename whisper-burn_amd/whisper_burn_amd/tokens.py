@@ -30,6 +30,8 @@ class SpecialTokens:
     start_of_prev: int = -1     # <|startofprev|> (transcribe.rs:181); only the optional prompt-conditioning mode uses it
     language_ids: tuple = ()    # every language token of the vocabulary, ascending (empty: English-only); detect_language
     no_speech: int = -1         # <|nospeech|> (<|nocaptions|> in the original vocabulary files); -1: none
+    timestamp_begin: int = 0    # <|0.00|>: ids [timestamp_begin, timestamp_begin + n_timestamps) are the timestamp tokens
+    n_timestamps: int = 0       # 1501 in Whisper's vocabularies (0.00 .. 30.00 s in 0.02 s steps); 0: the vocabulary has none
 
     @staticmethod
     def for_vocab(n_vocab: int, language_index: int = 0) -> "SpecialTokens":
@@ -40,11 +42,13 @@ class SpecialTokens:
             lang0, transcribe, notimestamps = 50258, 50358, 50362
             sop = 50360
             langs, nsp = (), 50361           # the .en vocabulary keeps the slots, the checkpoint knows one language
+            ts0, nts = 50363, 1501
         elif n_vocab == 51865:
             eot, sot = 50257, 50258
             lang0, transcribe, notimestamps = 50259, 50359, 50363
             sop = 50361
             langs, nsp = tuple(range(50259, 50358)), 50362   # 99 slots between sot and <|translate|>
+            ts0, nts = 50364, 1501
         else:
             assert n_vocab >= 32
             eot = n_vocab - 16
@@ -52,9 +56,38 @@ class SpecialTokens:
             sop = eot + 5
             language_index = 0
             langs, nsp = (eot + 2, eot + 3), -1     # two language slots (en, zh), no no-speech token
+            ts0, nts = 0, 0                         # ... and no timestamp block (a test names a range of its own)
         is_special = np.zeros(n_vocab, dtype=np.uint8)
         is_special[eot:] = 1
-        return SpecialTokens(sot, lang0 + language_index, transcribe, notimestamps, eot, is_special, sop, langs, nsp)
+        return SpecialTokens(sot, lang0 + language_index, transcribe, notimestamps, eot, is_special, sop, langs, nsp, ts0, nts)
+
+
+# Whisper's non-speech symbols (tokenizer.py: non_speech_tokens): suppressed so that the transcript carries no annotations
+NON_SPEECH_SYMBOLS = tuple('"#()*+/:;<=>@[\\]^_`{|}~「」『』') + (
+    "<<", ">>", "<<<", ">>>", "--", "---", "-(", "-[", "('", '("', "((", "))", "(((", ")))", "[[", "]]", "{{", "}}", "♪♪", "♪♪♪",
+    "♩", "♪", "♫", "♬", "♭", "♮", "♯")
+
+
+def default_suppress(st: SpecialTokens, tokenizer: "TokenizerAdapter" = None):
+    """Whisper's default static masks for timestamp decoding, (suppress, suppress_first) as uint8 [V]: suppress = every
+    special token but end-of-text and the timestamps -- with a tokenizer also the non-speech symbols (the ids that encode
+    a symbol alone or behind a space) --; suppress_first = end-of-text -- with a tokenizer also the blank " "."""
+    V = len(st.is_special)
+    sup = (np.asarray(st.is_special) != 0).astype(np.uint8)
+    sup[st.end_of_text] = 0
+    sup[st.timestamp_begin:st.timestamp_begin + st.n_timestamps] = 0
+    first = np.zeros(V, dtype=np.uint8)
+    first[st.end_of_text] = 1
+    if tokenizer is not None:
+        for sym in NON_SPEECH_SYMBOLS:
+            for text in (sym, " " + sym):
+                ids = tokenizer.tok.encode(text, add_special_tokens=False).ids
+                if len(ids) == 1 and 0 <= ids[0] < V:
+                    sup[ids[0]] = 1
+        ids = tokenizer.tok.encode(" ", add_special_tokens=False).ids
+        if len(ids) == 1:
+            first[ids[0]] = 1
+    return sup, first
 
 
 # ---- tokenizer integration (src/token.rs) -------------------------------------------------------------------
@@ -106,7 +139,17 @@ class TokenizerAdapter:
         sop = self.special_token(special_token_name("startofprev"))
         return SpecialTokens(ids["startoftranscript"], ids["language"], ids["transcribe"], ids["notimestamps"],
                              ids["endoftext"], mask, -1 if sop is None else int(sop),
-                             tuple(t for _, t in self.language_tokens()), self.no_speech_token())
+                             tuple(t for _, t in self.language_tokens()), self.no_speech_token(), *self.timestamp_range())
+
+    def timestamp_range(self):
+        """(id of <|0.00|>, number of consecutive <|x.xx|> tokens from it); (0, 0) when the tokenizer has none."""
+        t0 = self.special_token("<|0.00|>")
+        if t0 is None:
+            return 0, 0
+        n = 0
+        while self.special_token("<|%.2f|>" % (0.02 * n)) == int(t0) + n:
+            n += 1
+        return int(t0), n
 
     def language_tokens(self):
         """(abbreviation, id) of every language token the tokenizer knows, in LANGUAGES order."""

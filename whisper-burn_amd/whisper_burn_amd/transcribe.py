@@ -28,6 +28,10 @@ Optional with it: `--temperatures 0,0.2,...` (the first must be 0), `--best-of N
 holds the per-window lines only, and each gains `temperature` and `status` (0 accepted, 1 failed every temperature, 2 no
 speech).
 
+`--segments PATH` decodes WITH timestamp tokens (wb_waveform_to_segments: Whisper's timestamp rules on the device, the
+window moves by the last decoded timestamp) and writes one JSON line per segment, {"start", "end", "text", "tokens"} with
+times in seconds; the transcript is then the segments' text.  Not together with --fallback, --token-times or --scores.
+
 One addition: with `WHISPER_HIP_RESAMPLE=1` in the environment a mono WAV of another sample rate (the bundled
 22 050 Hz audio.wav, which the reference sends through `sox`, README.md:69-74) is resampled to 16 kHz on the GPU
 (wb_resample_dev) instead of being rejected.
@@ -49,9 +53,10 @@ def main(argv=None) -> int:
     frontend = None
     times_file = None
     scores_file = None
+    segments_file = None
     extra = argv[5:]
     usage = (f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference] "
-             f"[--token-times PATH] [--scores PATH] [--fallback [--temperatures T0,T1,..] [--best-of N] [--seed N] "
+             f"[--token-times PATH] [--scores PATH] [--segments PATH] [--fallback [--temperatures T0,T1,..] [--best-of N] [--seed N] "
              f"[--logprob-threshold X] [--no-speech-threshold X] [--compression-ratio-threshold X]]")
     fallback = False
     fb = {}                                     # keyword arguments of FallbackParams given on the command line
@@ -71,7 +76,7 @@ def main(argv=None) -> int:
                 print(usage, file=sys.stderr)
                 return 1
             extra = extra[2:]
-        elif extra[0] in ("--frontend", "--token-times", "--scores"):
+        elif extra[0] in ("--frontend", "--token-times", "--scores", "--segments"):
             if len(extra) < 2 or (extra[0] == "--frontend" and extra[1] not in ("fft", "reference")):
                 print(usage, file=sys.stderr)
                 return 1
@@ -79,6 +84,8 @@ def main(argv=None) -> int:
                 frontend = extra[1]
             elif extra[0] == "--scores":
                 scores_file = extra[1]
+            elif extra[0] == "--segments":
+                segments_file = extra[1]
             else:
                 times_file = extra[1]
             extra = extra[2:]
@@ -89,6 +96,10 @@ def main(argv=None) -> int:
         return 1
     if fallback and times_file is not None:
         print("--token-times is not available together with --fallback\n" + usage, file=sys.stderr)
+        return 1
+    if segments_file is not None and (fallback or times_file is not None or scores_file is not None):
+        print("--segments (decoding with timestamp tokens) is not available together with --fallback, --token-times or --scores\n"
+              + usage, file=sys.stderr)
         return 1
     if lang != "auto" and lang not in LANGUAGES:
         print(f"Invalid language abbreviation: {lang}", file=sys.stderr)
@@ -153,8 +164,18 @@ def main(argv=None) -> int:
     token_times = None
     scores = None
     fb_result = None
+    segments = None
     try:
-        if fallback:
+        if segments_file is not None:
+            # decoding WITH timestamp tokens: the window moves by the last decoded timestamp, the text is the segments' text
+            from .tokens import default_suppress
+            st = bpe.special_tokens(lang)
+            if st.n_timestamps == 0:
+                raise ValueError("the tokenizer has no timestamp tokens (<|0.00|> ...)")
+            sup, sup_first = default_suppress(st, bpe)
+            segments, _tokens, _ = wb.waveform_to_segments(whisper, st, waveform, sample_rate, suppress=sup, suppress_first=sup_first)
+            text = bpe.decode(_tokens, True)
+        elif fallback:
             st = bpe.special_tokens(lang)
             fb_result = wb.waveform_to_tokens_fallback(whisper, st, waveform, sample_rate,
                                                        fallback=wb.FallbackParams(tok_no_speech=st.no_speech, **fb),
@@ -180,6 +201,16 @@ def main(argv=None) -> int:
     except OSError as e:
         print(f"Error writing transcription file: {e}", file=sys.stderr)
         return 1
+    if segments_file is not None:
+        import json
+        try:
+            with open(segments_file, "w") as fh:
+                for seg in segments:
+                    fh.write(json.dumps({"start": round(seg["start"], 2), "end": round(seg["end"], 2),
+                                         "text": bpe.decode(seg["tokens"], True), "tokens": [int(t) for t in seg["tokens"]]}) + "\n")
+        except OSError as e:
+            print(f"Error writing segments file: {e}", file=sys.stderr)
+            return 1
     if times_file is not None:
         import json
         import math
