@@ -136,6 +136,7 @@ struct CrossLds {
   float pbuf[CMAX];
   alignas(16) float part[32][64];
   alignas(16) float att[64];
+  alignas(16) float wmax[8];                       // the waves' score maxima
   alignas(16) float obuf[(G - 1) * d];
 };
 
@@ -1133,7 +1134,7 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
   static_assert(G == CrossLds<DPL, NP>::G && CMAX == CrossLds<DPL, NP>::CMAX && RG::SL == SL && RG::NTILE == NTILE && RG::RPG == RPG &&
                 NT == ROLE_NT, "LDS struct / resident geometry");
   auto& hs = sm.hs; auto& red = sm.red; auto& qv = sm.qv; auto& sc = sm.sc; auto& pbuf = sm.pbuf; auto& part = sm.part; auto& att = sm.att;
-  auto& obuf = sm.obuf;
+  auto& obuf = sm.obuf; auto& wmax = sm.wmax;
   const bool res_v = RG::NVT > 0 && res != nullptr;     // (block-uniform)
   const int tid = role_tid<PS>(), lane = tid & 63, wave = tid >> 6;
   if (h >= a.n_head) return true;
@@ -1352,15 +1353,40 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
   }
   __syncthreads();
   if constexpr (PS) ps_stamp(ps, 4);
-  // softmax statistics, redundantly per wave (no extra barrier); then the probabilities, two keys per thread
-  float m = -INFINITY;
-  for (int j = lane; j < C; j += 64) m = fmaxf(m, sc[j]);
-  m = wave_max(m);
-  float l = 0.f;
-  for (int j = lane; j < C; j += 64) l += expf(sc[j] - m);
-  l = wave_sum(l);
-  for (int j = tid; j < C; j += NT) pbuf[j] = expf(sc[j] - m);
+  // softmax over the block, every score read once and every exponential computed once: thread tid owns keys tid + 512 i
+  // (compile-time trip count: the LDS reads are issued together).  The maximum meets in LDS per wave (one barrier; maxima
+  // do not depend on the order), the probabilities go to pbuf, and the denominator is summed from pbuf by the wave that
+  // divides by it (below): lane, then key, ascending, then the wave_sum tree -- the order of the former per-wave loop, so
+  // l keeps its bits.
+  constexpr int KPT = (CMAX + NT - 1) / NT;        // keys per thread
+  float m;
+  {
+    float sv[KPT];
+#pragma unroll
+    for (int i = 0; i < KPT; i++) sv[i] = sc[min(tid + NT * i, CMAX - 1)];
+    float mt = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < KPT; i++) mt = fmaxf(mt, tid + NT * i < C ? sv[i] : -INFINITY);
+    mt = wave_max(mt);
+    if (lane == 0) wmax[wave] = mt;
+    __syncthreads();
+    const float4 m0 = *reinterpret_cast<const float4*>(&wmax[0]), m1 = *reinterpret_cast<const float4*>(&wmax[4]);
+    m = fmaxf(fmaxf(fmaxf(m0.x, m0.y), fmaxf(m0.z, m0.w)), fmaxf(fmaxf(m1.x, m1.y), fmaxf(m1.z, m1.w)));
+#pragma unroll
+    for (int i = 0; i < KPT; i++)
+      if (tid + NT * i < C) pbuf[tid + NT * i] = expf(sv[i] - m);
+  }
   __syncthreads();
+  float l = 0.f;
+  if (tid < 64) {                                  // (the wave of the division below)
+    constexpr int KPL = CMAX / 64;
+    float pv[KPL];
+#pragma unroll
+    for (int i = 0; i < KPL; i++) pv[i] = pbuf[lane + 64 * i];
+#pragma unroll
+    for (int i = 0; i < KPL; i++) l += lane + 64 * i < C ? pv[i] : 0.f;
+    l = wave_sum(l);
+  }
   // ---- o[c4 .. c4 + 3] partial over this thread's keys (tile, slot ascending), then over the 32 row groups
   {
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);

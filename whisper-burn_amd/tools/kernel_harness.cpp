@@ -412,6 +412,67 @@ int wbk_align_dtw(WbkDtw* t) {
   return P.err ? P.err : status;
 }
 
+// launch_dec_cross_fused (decode_fused.hip): one fused cross-attention sublayer step over n_rows live rows.  The step state is
+// assembled here (st[ST_N] = n_rows, row r belongs to window row_win[r], no row dead).  x_in / x_out [S][d], pend [KSp][S][d],
+// ckv: cached K | V rows (V of a key sits d floats behind its K), win_row0 / win_C [W], P [n_head][S][d] (copied in and back).
+struct WbkCross {
+  WbkBuf x_in, pend, pbias, x_out, ln_g, ln_b, Wq, bq, ckv, win_row0, win_C, row_win, Wo, P;
+  int64_t S, W, d, n_head, KSp, ldkv, koff, n_pass, n_rows, ln_inside;
+  double ln_eps, scale;
+};
+
+int wbk_cross_fused_ring() { return wb::CROSS_FUSED_MAX_C; }   // keys one pass of this build's ring holds
+
+int wbk_cross_fused(WbkCross* t) {
+  const int64_t S = t->S, W = t->W, d = t->d, H = t->n_head, n = t->n_rows;
+  if (!wb::dec_fused_supported((int)d) || H * 64 != d || S < 1 || S > 64 || n < 1 || n > S || W < 1 || W > 64) return WBK_EARG;
+  if (t->n_pass < 1 || t->n_pass > wb::CROSS_FUSED_MAX_PASSES || t->KSp < 0 || t->KSp > 64) return WBK_EARG;
+  if (t->ldkv % 4 || t->koff % 4 || t->koff < 0 || t->ldkv < 2 * d || !aligned16(t->ckv, t->koff, 4)) return WBK_EARG;
+  const int32_t* r0 = (const int32_t*)t->win_row0.host; const int32_t* wc = (const int32_t*)t->win_C.host;
+  const int32_t* rw = (const int32_t*)t->row_win.host;
+  if (!r0 || !wc || !rw || t->win_row0.off || t->win_C.off || t->row_win.off || t->win_row0.bytes < W * 4 || t->win_C.bytes < W * 4 ||
+      t->row_win.bytes < n * 4)
+    return WBK_EARG;
+  for (int64_t w = 0; w < W; w++) {
+    if (wc[w] < 1 || wc[w] > t->n_pass * wb::CROSS_FUSED_MAX_C || r0[w] < 0) return WBK_EARG;
+    if (!inside(t->ckv, t->koff + (int64_t)r0[w] * t->ldkv, t->koff + ((int64_t)r0[w] + wc[w] - 1) * t->ldkv + 2 * d, 4)) return WBK_EARG;
+    if (((int64_t)r0[w] + wc[w]) * t->ldkv + t->koff + 2 * d >= (1ll << 31)) return WBK_EARG;   // (32-bit row offsets)
+  }
+  for (int64_t r = 0; r < n; r++) if (rw[r] < 0 || rw[r] >= W) return WBK_EARG;
+  if (!inside(t->x_in, 0, S * d, 4) || !inside(t->x_out, 0, S * d, 4) || !inside(t->P, 0, H * S * d, 4) || !aligned16(t->P, 0, 4))
+    return WBK_EARG;
+  if (t->KSp > 0 && (!inside(t->pend, 0, t->KSp * S * d, 4) || !inside(t->pbias, 0, d, 4))) return WBK_EARG;
+  if (!inside(t->ln_g, 0, d, 4) || !inside(t->ln_b, 0, d, 4) || !inside(t->bq, 0, d, 4)) return WBK_EARG;
+  if (!inside(t->Wq, 0, d * d, 4) || !inside(t->Wo, 0, d * d, 4) || !aligned16(t->Wq, 0, 4) || !aligned16(t->Wo, 0, 4)) return WBK_EARG;
+
+  const wb::StepLayout lay = wb::make_step_layout((int)S, (int)W);
+  std::vector<int32_t> st((size_t)lay.total, 0);
+  st[wb::ST_N] = (int32_t)n;
+  for (int64_t r = 0; r < n; r++) st[(size_t)(lay.win + r)] = rw[r];
+  const WbkBuf stb{st.data(), (int64_t)st.size() * 4, 0};
+
+  Pool P;
+  char *dst = upload(P, stb), *dx = upload(P, t->x_in), *dpe = upload(P, t->pend), *dpb = upload(P, t->pbias), *dxo = upload(P, t->x_out);
+  char *dg = upload(P, t->ln_g), *db = upload(P, t->ln_b), *dWq = upload(P, t->Wq), *dbq = upload(P, t->bq), *dkv = upload(P, t->ckv);
+  char *dr0 = upload(P, t->win_row0), *dwc = upload(P, t->win_C), *dWo = upload(P, t->Wo), *dP = upload(P, t->P);
+  if (P.err) return P.err;
+  auto at = [](char* p, const WbkBuf& b) -> char* { return p ? p + b.off : nullptr; };
+  wb::CrossFusedArgs a;
+  a.st = (const int*)dst; a.lay = lay; a.S = (int)S; a.d = (int)d; a.n_head = (int)H;
+  a.x_in = (const float*)at(dx, t->x_in); a.pend = t->KSp > 0 ? (const float*)at(dpe, t->pend) : nullptr; a.KSp = (int)t->KSp;
+  a.pbias = t->KSp > 0 ? (const float*)at(dpb, t->pbias) : nullptr; a.x_out = (float*)at(dxo, t->x_out);
+  a.ln_g = (const float*)at(dg, t->ln_g); a.ln_b = (const float*)at(db, t->ln_b); a.ln_eps = (float)t->ln_eps; a.ln_inside = (int)t->ln_inside;
+  a.Wq = (const float*)at(dWq, t->Wq); a.bq = (const float*)at(dbq, t->bq); a.scale = (float)t->scale;
+  a.ckv = (const float*)at(dkv, t->ckv); a.ldkv = (int)t->ldkv; a.koff = (int)t->koff;
+  a.win_row0 = (const int*)dr0; a.win_C = (const int*)dwc; a.n_pass = (int)t->n_pass;
+  a.Wo = (const float*)at(dWo, t->Wo); a.P = (float*)at(dP, t->P);
+  wb::launch_dec_cross_fused(nullptr, a, (int)n);
+  const int status = finish(P, 0);
+  if (status) return status;
+  download(P, t->x_out, dxo); download(P, t->P, dP);
+  return P.err;
+}
+
 const char* wbk_version() { return "whisper_hip kernel test harness 1"; }
 
 }  // extern "C"
