@@ -643,6 +643,93 @@ int wb_waveform_to_segments(wb_model* m, const float* pcm, int64_t n, int sample
                             int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap, int32_t* n_segments,
                             int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens, int32_t* n_windows);
 
+/* ---- beam search under the timestamp rules (an extension: Whisper's BeamSearchDecoder on the device) ------------------
+ * Per window, with B = beam_size and C = max_candidates = round-half-even(B * patience), computed once on the host:
+ *   1. One live beam holds the prompt with cumulative score 0.0 (Whisper's B identical copies collapse to it: its
+ *      candidate dictionary is keyed by sequence).
+ *   2. Each live beam j has its own rule state (gen_j: last / penultimate token a timestamp, last timestamp); n_gen, the
+ *      depth, is the same for all.  Its allowed set is rules (a) - (f) above with suppress / suppress_first;
+ *      lp_v = x_v - logsumexp(allowed) in f32; its candidates are its min(B + 1, |allowed|) best ids by (logit descending,
+ *      id ascending); a candidate's score is score_j + (double)lp_v.
+ *   3. All candidates of the window are sorted by (score descending, beam index ascending, rank within the beam
+ *      ascending) and walked: an end-of-text candidate goes to this step's newly finished list, any other becomes a live
+ *      beam of the next step; the walk stops behind the B-th live beam (end-of-text candidates ranked behind that point
+ *      are dropped).  Fewer than B other candidates: fewer live beams (Whisper would fail; this engine goes on).
+ *   4. The newly finished are appended to the window's store in walk order while it holds fewer than C; the rest is
+ *      dropped.  The window ends when the store holds C entries, no live beam is left or max_depth steps have run --
+ *      each window by itself.
+ *   5. Finalize (host): a store with fewer than B entries is filled up with the live beams in descending score order
+ *      (ties: lower beam index); they keep their score and carry no end-of-text.  rank = score / n_text when
+ *      length_penalty < 0 (n_text: tokens without the end-of-text; n_text == 0 ranks -inf), else
+ *      score / ((5 + n_text) / 6)^length_penalty.  The result is the first of equal maxima in store order.
+ *   6. A child's rule state is its parent's, updated by the child's token.
+ * Deviations from Whisper: ties (equal scores) are ordered as in 3; windows end individually; fewer than B live beams
+ * are accepted; scores are f64 sums of f32 log-probs. */
+typedef struct wb_beam_params {
+  int32_t beam_size;      /* 5; 1 .. 7 and <= the session's max_beams */
+  float patience;         /* 1.0; >= 1, max_candidates <= 16 */
+  float length_penalty;   /* -1 (any negative value): rank by score / n_text; >= 0: Google NMT's ((5 + n) / 6)^alpha */
+} wb_beam_params;
+void wb_beam_params_default(wb_beam_params* p);   /* 5, 1.0, -1 */
+/* wb_session_decode_timestamps by beam search, on a fresh or rewound session: candidates and bookkeeping run on the
+ * device, chunks of steps replay as one graph -- the same graph for every rule parameter, patience and length penalty.
+ * prompt, active, out_tokens [W][row_stride] (prompt + the best candidate) and out_lens as there; out_score [W] the best
+ * candidate's cumulative log-prob and out_n_candidates [W] the number of finalized candidates (both may be NULL).  p
+ * supplies max_depth and tok_end_of_text; tp the rules.  A NaN logit, an allowed +inf logit, a live beam without an
+ * allowed id or a NaN score ends that beam on end-of-text and fails the call with WB_ERR_STATE.
+ * Errors with nothing launched (WB_ERR_ARG): tp->temperature != 0, tp->best_of != 1, beam_size outside [1, 7] or above the
+ * session's max_beams, patience < 1 or not finite, max_candidates > 16, length_penalty not finite, and those of
+ * wb_session_decode_timestamps; wb_session_set_suppress not called -> WB_ERR_STATE. */
+int wb_session_decode_timestamps_beam(wb_session* s, const wb_decode_params* p, const wb_timestamp_params* tp,
+                                      const wb_beam_params* bp, const int32_t* prompt, int32_t prompt_len,
+                                      const uint8_t* active, int32_t* out_tokens, int32_t row_stride, int32_t* out_lens,
+                                      double* out_score, int32_t* out_n_candidates);
+/* Every finalized candidate of the last wb_session_decode_timestamps_beam, in store order: n [W] candidates per window
+ * (-1: the window was not active; at most cap are written, cap = 16 always suffices), tokens [W][cap][row_stride] the
+ * generated tokens (no prompt), lens / scores / ranks [W][cap]. */
+int wb_session_last_beams(wb_session* s, int32_t cap, int32_t* tokens, int32_t row_stride, int32_t* lens, double* scores,
+                          double* ranks, int32_t* n);
+/* The trace of the last wb_session_decode_timestamps_beam: n_steps [W] steps the window took part in; for step t <
+ * max_steps and window w: n_live [t][W] live beams behind the step, n_finished [t][W] candidates newly finished in it
+ * (before the store's cap), and per live beam q < n_live the token, the index of its parent among the live beams in front
+ * of the step and its f64 score: tokens / parents / scores [t][W][8]. */
+int wb_session_last_beam_trace(wb_session* s, int32_t max_steps, int32_t* n_steps, int32_t* n_live, int32_t* n_finished,
+                               int32_t* tokens, int32_t* parents, double* scores);
+/* Test hook: the candidates of dec_tsbeam_rows_kernel alone on caller data (wb_timestamp_rows' inputs at temperature 0,
+ * plus k in [1, 8]).  out_ids / out_logprobs [R][k]: the row's min(k, |allowed|) best allowed ids in (logit descending, id
+ * ascending) order with x - logsumexp(allowed) (entries past the count are not written); out_count / out_forced [R];
+ * out_stats [R][2] = (ts_lse, mN).  A row with a NaN logit or without an allowed id gives the single candidate eot with
+ * log-prob 0 and *out_err = 1.  Outputs sit between guard bands on the device. */
+int wb_timestamp_beam_rows(int device, const float* logits, int32_t R, int32_t ld, int32_t V, const uint8_t* suppress,
+                           const uint8_t* suppress_first, int32_t tok_timestamp_begin, int32_t n_timestamps,
+                           int32_t max_initial_timestamp_index, int32_t max_timestamp_index, const int32_t* n_gen,
+                           const int32_t* prev1, const int32_t* prev2, const int32_t* last_ts, int32_t eot, int32_t k,
+                           int32_t* out_ids, float* out_logprobs, int32_t* out_count, int32_t* out_forced, float* out_stats,
+                           int32_t* out_err);
+/* Fills the logits [n][V] of the n live rows of step `step` (0-based).  Row i is live beam beam[i] of window window[i];
+ * behind step 0 it holds the prompt (token[i] = -1, parent[i] = -1), later the token it was extended by and the index of
+ * its parent among the previous step's live beams of that window.  Returns 0, or an error code that ends the search. */
+typedef int (*wb_tsbeam_logits_fn)(void* user, int32_t step, int32_t n, const int32_t* window, const int32_t* beam,
+                                   const int32_t* token, const int32_t* parent, float* logits);
+/* Test hook without a model: both kernels of the beam search driven by a caller callback, the counterpart of
+ * wb_beam_search_device.  n_windows <= 64 windows of a vocabulary of V ids; results as wb_session_last_beams (cap = 16,
+ * row_stride >= max_depth) and wb_session_last_beam_trace (max_steps = max_depth) write them, plus best [W] = the index of
+ * the returned candidate. */
+int wb_timestamp_beam_search_device(int device, const wb_timestamp_params* tp, const wb_beam_params* bp, int32_t n_windows,
+                                    int32_t V, const uint8_t* suppress, const uint8_t* suppress_first, int32_t eot,
+                                    int32_t max_depth, wb_tsbeam_logits_fn fill, void* user, int32_t* cand_tokens,
+                                    int32_t row_stride, int32_t* cand_lens, double* cand_scores, double* cand_ranks,
+                                    int32_t* n_cand, int32_t* best, int32_t* n_steps, int32_t* n_live, int32_t* n_finished,
+                                    int32_t* tr_tokens, int32_t* tr_parents, double* tr_scores);
+/* wb_waveform_to_segments with every window decoded by wb_session_decode_timestamps_beam (sessions of max_beams =
+ * beam_size). */
+int wb_waveform_to_segments_beam(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                                 const wb_timestamp_params* tp, const wb_beam_params* bp, const uint8_t* suppress,
+                                 const uint8_t* suppress_first, const int32_t* prompt, int32_t prompt_len, float* seg_start,
+                                 float* seg_end_time, int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap,
+                                 int32_t* n_segments, int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens,
+                                 int32_t* n_windows);
+
 /* The reference's retired greedy decoder kept its repetition detectors (transcribe.rs:385-447, dead code there):
  *   wb_first_repetition_end        :385-393   (period > n, a usize underflow panic there -> WB_ERR_ARG)
  *   wb_repetition_period           :395-417   returns the period, 0 for None

@@ -86,6 +86,19 @@ pub struct wb_timestamp_params {
     pub attempt: i32,
 }
 
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct wb_beam_params {
+    pub beam_size: i32,
+    pub patience: c_float,
+    pub length_penalty: c_float,
+}
+
+/// Fills the logits `[n][V]` of the live rows of one step of `wb_timestamp_beam_search_device` (a test hook).
+pub type wb_tsbeam_logits_fn = Option<unsafe extern "C" fn(user: *mut c_void, step: i32, n: i32, window: *const i32,
+                                                           beam: *const i32, token: *const i32, parent: *const i32,
+                                                           logits: *mut c_float) -> c_int>;
+
 /// Compression ratio of one window's generated tokens, computed on the caller's side (it owns the tokenizer).
 pub type wb_ratio_fn = Option<unsafe extern "C" fn(user: *mut c_void, tokens: *const i32, n: i32) -> c_double>;
 
@@ -192,6 +205,18 @@ extern "C" {
                                    seg_begin: *mut i32, seg_end: *mut i32, seg_start: *mut c_float,
                                    seg_end_time: *mut c_float, cap: i32, n_segments: *mut i32,
                                    advance_index: *mut i32) -> c_int;
+    // beam search under the timestamp rules: results of the last call, the rows kernel's test hook
+    pub fn wb_session_last_beams(s: *mut wb_session, cap: i32, tokens: *mut i32, row_stride: i32, lens: *mut i32,
+                                 scores: *mut c_double, ranks: *mut c_double, n: *mut i32) -> c_int;
+    pub fn wb_session_last_beam_trace(s: *mut wb_session, max_steps: i32, n_steps: *mut i32, n_live: *mut i32,
+                                      n_finished: *mut i32, tokens: *mut i32, parents: *mut i32,
+                                      scores: *mut c_double) -> c_int;
+    pub fn wb_timestamp_beam_rows(device: c_int, logits: *const c_float, R: i32, ld: i32, V: i32, suppress: *const u8,
+                                  suppress_first: *const u8, tok_timestamp_begin: i32, n_timestamps: i32,
+                                  max_initial_timestamp_index: i32, max_timestamp_index: i32, n_gen: *const i32,
+                                  prev1: *const i32, prev2: *const i32, last_ts: *const i32, eot: i32, k: i32,
+                                  out_ids: *mut i32, out_logprobs: *mut c_float, out_count: *mut i32,
+                                  out_forced: *mut i32, out_stats: *mut c_float, out_err: *mut i32) -> c_int;
     pub fn wb_session_begin(m: *mut wb_model, pcm: *const c_float, n_pcm: i64, starts: *const i64, lens: *const i64,
                             n_windows: c_int, max_beams: c_int, padding: c_int, out: *mut *mut wb_session) -> c_int;
     pub fn wb_session_set_special_mask(s: *mut wb_session, is_special: *const u8) -> c_int;
@@ -238,6 +263,25 @@ extern "C" {
                                    seg_start: *mut c_float, seg_end_time: *mut c_float, seg_tok_begin: *mut i32,
                                    seg_tok_end: *mut i32, seg_cap: i32, n_segments: *mut i32, text_tokens: *mut i32,
                                    text_cap: i64, n_text_tokens: *mut i64, n_windows: *mut i32) -> c_int;
+    pub fn wb_beam_params_default(p: *mut wb_beam_params);
+    pub fn wb_session_decode_timestamps_beam(s: *mut wb_session, p: *const wb_decode_params, tp: *const wb_timestamp_params,
+                                             bp: *const wb_beam_params, prompt: *const i32, prompt_len: i32,
+                                             active: *const u8, out_tokens: *mut i32, row_stride: i32, out_lens: *mut i32,
+                                             out_score: *mut c_double, out_n_candidates: *mut i32) -> c_int;
+    pub fn wb_timestamp_beam_search_device(device: c_int, tp: *const wb_timestamp_params, bp: *const wb_beam_params,
+                                           n_windows: i32, V: i32, suppress: *const u8, suppress_first: *const u8, eot: i32,
+                                           max_depth: i32, fill: wb_tsbeam_logits_fn, user: *mut c_void,
+                                           cand_tokens: *mut i32, row_stride: i32, cand_lens: *mut i32,
+                                           cand_scores: *mut c_double, cand_ranks: *mut c_double, n_cand: *mut i32,
+                                           best: *mut i32, n_steps: *mut i32, n_live: *mut i32, n_finished: *mut i32,
+                                           tr_tokens: *mut i32, tr_parents: *mut i32, tr_scores: *mut c_double) -> c_int;
+    pub fn wb_waveform_to_segments_beam(m: *mut wb_model, pcm: *const c_float, n: i64, sample_rate: c_int,
+                                        p: *const wb_decode_params, tp: *const wb_timestamp_params,
+                                        bp: *const wb_beam_params, suppress: *const u8, suppress_first: *const u8,
+                                        prompt: *const i32, prompt_len: i32, seg_start: *mut c_float,
+                                        seg_end_time: *mut c_float, seg_tok_begin: *mut i32, seg_tok_end: *mut i32,
+                                        seg_cap: i32, n_segments: *mut i32, text_tokens: *mut i32, text_cap: i64,
+                                        n_text_tokens: *mut i64, n_windows: *mut i32) -> c_int;
     pub fn wb_fallback_params_default(p: *mut wb_fallback_params);
     pub fn wb_fallback_decide(fp: *const wb_fallback_params, avg_logprob: c_float, no_speech_prob: c_float,
                               ratio: c_float) -> c_int;

@@ -275,6 +275,70 @@ struct TsRowsArgs {
 };
 void launch_ts_rows(hipStream_t st, const TsRowsArgs& a);
 
+// ---- beam search under the timestamp rules (tsbeam.hip, tsbeam_chain.cpp) ------------------------------------------
+// Whisper's BeamSearchDecoder on the device, per window: dec_tsbeam_rows_kernel (one block per live row, behind the logits
+// tail) leaves the row's B + 1 best allowed ids with their log-probs under the filtered log-softmax;
+// dec_tsbeam_update_kernel (one wave per window) ranks the window's candidates by f64 cumulative score, walks them into the
+// next live beams and the finished store, carries each child's rule state over from its parent and writes the next step's
+// state block.  B, C = max_candidates and every rule parameter live in the control block: one captured graph serves every
+// rule setting and patience.
+enum { TB_DEPTH = 0, TB_ALLDONE = 1, TB_ERR = 2, TB_NENDED = 3, TB_NWIN = 4, TB_B = 5, TB_C = 6, TB_TB = 7, TB_NTS = 8,
+       TB_MAX_INIT = 9, TB_MAX_TS = 10, TB_NLIVE = 11, TB_HDR = 16 };
+struct TsBeamLayout {
+  int S = 0, W = 0, max_depth = 0;
+  // int offsets.  Per window: nb (live beams), ended, nfin (store entries) [W]; per live beam slot / node / last_was /
+  // penult_was / last_ts [W][MAX_BEAMS]; store nodes fin_node [W][BEAM_KB] (the node the end-of-text hangs on, -1: the
+  // prompt); per row (slot) its beam index row_beam [S]; the trace tr_n / tr_fin [max_depth][W].  Then doubles (8-byte
+  // aligned): score [W][MAX_BEAMS], fin_score [W][BEAM_KB], tr_score [max_depth][W][MAX_BEAMS].  Then the node tree
+  // int2 (token, parent node) [max_depth][W][MAX_BEAMS]: node (t W + w) MAX_BEAMS + q is live beam q of window w behind step t.
+  int nb = 0, ended = 0, nfin = 0, slot = 0, node = 0, last_was = 0, penult_was = 0, last_ts = 0, fin_node = 0, row_beam = 0,
+      tr_n = 0, tr_fin = 0, score = 0, fin_score = 0, tr_score = 0, nodes = 0, total_ints = 0;
+};
+inline TsBeamLayout make_tsbeam_layout(int S, int W, int max_depth) {
+  TsBeamLayout b;
+  b.S = S; b.W = W; b.max_depth = max_depth;
+  const int WB = W * MAX_BEAMS, DW = max_depth * W;
+  b.nb = TB_HDR; b.ended = b.nb + W; b.nfin = b.ended + W; b.slot = b.nfin + W; b.node = b.slot + WB; b.last_was = b.node + WB;
+  b.penult_was = b.last_was + WB; b.last_ts = b.penult_was + WB; b.fin_node = b.last_ts + WB; b.row_beam = b.fin_node + W * BEAM_KB;
+  b.tr_n = b.row_beam + S; b.tr_fin = b.tr_n + DW;
+  b.score = (b.tr_fin + DW + 1) & ~1;
+  b.fin_score = b.score + 2 * WB; b.tr_score = b.fin_score + 2 * W * BEAM_KB;
+  b.nodes = b.tr_score + 2 * DW * MAX_BEAMS;
+  b.total_ints = b.nodes + 2 * DW * MAX_BEAMS;
+  return b;
+}
+// what the rows kernel leaves per row behind the [S][TOPK_MAX] id / log-prob arrays: int[S][4]
+enum { TBR_COUNT = 0, TBR_FORCED = 1, TBR_TS_LSE = 2, TBR_MN = 3, TBR_STRIDE = 4 };   // [2], [3]: the bits of the f32 statistics
+struct TsBeamRowsArgs {
+  int* ctl = nullptr; TsBeamLayout bl;
+  const float* logits = nullptr; int V = 0;                            // the step's unmasked logits [S][V]
+  const uint32_t* sup = nullptr; const uint32_t* sup_first = nullptr;  // as TsChainArgs
+  const int* state = nullptr; StepLayout lay;
+  int eot = 0;
+  int32_t* topk_id = nullptr; float* topk_lp = nullptr; int* row_out = nullptr;   // [S][TOPK_MAX] x 2, [S][TBR_STRIDE]
+};
+struct TsBeamUpdateArgs {
+  int* ctl = nullptr; TsBeamLayout bl;
+  const int32_t* topk_id = nullptr; const float* topk_lp = nullptr; const int* row_out = nullptr;
+  int* state = nullptr; StepLayout lay;                                // the step state block (device memory), rewritten
+  int eot = 0, V = 0;
+  int step_pos = 0;                                                    // position index (ST_STEP) of the first decode step
+  // the next step's position tables and embedding rows (x == nullptr: the scripted test hook has no model)
+  int* tabs = nullptr; int Lmax = 0; const float* E = nullptr; const float* pos = nullptr; int d = 0; float* x = nullptr;
+};
+void launch_dec_tsbeam_rows(hipStream_t st, const TsBeamRowsArgs& a, int n_rows);
+void launch_dec_tsbeam_update(hipStream_t st, const TsBeamUpdateArgs& a);
+// test hook (wb_timestamp_beam_rows): the rows kernel's device function alone, one block per row, on caller data
+struct TsBeamRowsHookArgs {
+  const float* logits = nullptr; int R = 0, ld = 0, V = 0, k = 0;
+  const uint32_t* sup = nullptr; const uint32_t* sup_first = nullptr;
+  TsRules rules;
+  const int32_t* n_gen = nullptr; const int32_t* prev1 = nullptr; const int32_t* prev2 = nullptr; const int32_t* last_ts = nullptr;
+  int32_t* out_id = nullptr; float* out_lp = nullptr;                  // [R][k]
+  int32_t* out_count = nullptr; int32_t* out_forced = nullptr; float* out_stats = nullptr; int32_t* out_err = nullptr;
+};
+void launch_tsbeam_rows_hook(hipStream_t st, const TsBeamRowsHookArgs& a);
+
 // ---- fused small-batch sublayer kernels (decode_fused.hip) ----------------------------------------------
 // Common prologue of both: x = x_in + (pbias + sum_s pend[s]) (KSp planes of [S][d]; KSp = 0: none), block 0
 // writes x to x_out, then LayerNorm(ln_g, ln_b, ln_eps).

@@ -329,8 +329,9 @@ static int enqueue_logits_tail(StepCtx& c, bool timed, bool merge_prepares, int*
   const BeamStepIO* bio = call.bio;
   const SampleStepIO* sio = call.sio;
   const TsStepIO* tio = call.tio;
-  int32_t* out_id_dev = bio ? bio->topk_id : sio ? sio->topk_id : tio ? tio->topk_id : reinterpret_cast<int32_t*>(s->host_block_dev + (size_t)L.total * 4);
-  float* out_lp_dev = bio ? bio->topk_lp : sio ? sio->topk_lp : tio ? tio->topk_lp
+  const TsBeamStepIO* tbio = call.tbio;
+  int32_t* out_id_dev = bio ? bio->topk_id : sio ? sio->topk_id : tio ? tio->topk_id : tbio ? tbio->topk_id : reinterpret_cast<int32_t*>(s->host_block_dev + (size_t)L.total * 4);
+  float* out_lp_dev = bio ? bio->topk_lp : sio ? sio->topk_lp : tio ? tio->topk_lp : tbio ? tbio->topk_lp
                           : reinterpret_cast<float*>(s->host_block_dev + (size_t)L.total * 4 + (size_t)S * TOPK_MAX * 4);
   const float* pend = s->P2.as<float>(); const float* pbias = m->dec[c.NL - 1].mlp2.b;   // what the last layer left pending
   if (!p.fuse_ln) c.resolve(pend, p.k2, pbias, m->ln_dec);
@@ -374,6 +375,12 @@ static int enqueue_logits_tail(StepCtx& c, bool timed, bool merge_prepares, int*
     prof_tag(KC_TS_UPDATE, 5.0 * (double)n * V);
     launch_dec_ts_update(st, tio->upd, n);
   }
+  if (tbio) {  // the rows read their logits twice (the second pass from L2); the bookkeeping reads the candidates
+    prof_tag(KC_TSBEAM_ROWS, 9.0 * (double)n * V);
+    launch_dec_tsbeam_rows(st, tbio->rows, n);
+    prof_tag(KC_TSBEAM_UPDATE, 12.0 * n * TOPK_MAX);
+    launch_dec_tsbeam_update(st, tbio->upd);
+  }
   if (timed && tm_logits.on) {
     WB_HIP(hipStreamSynchronize(st));
     tm_logits.collect();
@@ -396,7 +403,7 @@ static int enqueue_step(wb_session* s, const StepPlan& p, const StepCall& call, 
   // first step is prepared by session_greedy_chain)
   const bool merge_prepares = call.chained && p.fuse_ln;
   // (device-chained beam search / sampling: the bookkeeping launch behind the previous step prepared this one)
-  if (!merge_prepares && !bio && !call.sio && !call.tio) {
+  if (!merge_prepares && !bio && !call.sio && !call.tio && !call.tbio) {
     prof_tag(KC_PREPARE, 8.0 * c.n * c.d);
     launch_dec_prepare(c.st, hst, s->state.as<int>(), s->lay, c.n, c.tabs, s->Lmax, s->m->tok_emb, s->m->dec_pos, c.d, c.xb[0], gctl);
   }
@@ -412,7 +419,7 @@ int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call) {
   if (!plan.use_graph) {
     for (int i = 0; i < reps; i++) {
       WB_TRY(enqueue_step(s, plan, call, true));
-      if (call.chained || call.bio || call.sio || call.tio) s->prof_step_off++;
+      if (call.chained || call.bio || call.sio || call.tio || call.tbio) s->prof_step_off++;
     }
     return WB_OK;
   }
@@ -439,9 +446,9 @@ int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call) {
   // (the rest of the plan follows from n_launch, fuse_ln and what the signature above carries: the model, S, W, max_beams,
   // n_chunks, maxC -- and the process's switches)
   // (a sampling-chain graph bakes in its control block and max_depth: session_sample_chain drops ITS graphs when those change;
-  // a timestamp-chain graph likewise, and its suppress buffers: session_ts_chain)
+  // a timestamp-chain graph likewise, and its suppress buffers: session_ts_chain; so session_tsbeam_chain for its own)
   const uint64_t key = ((uint64_t)reps << 48) | ((uint64_t)plan.n_launch << 32) | ((uint64_t)call.k << 8) | (call.sio ? GRAPH_KEY_SAMPLE : 0u) |
-                       (call.tio ? GRAPH_KEY_TS : 0u) |
+                       (call.tio ? GRAPH_KEY_TS : 0u) | (call.tbio ? GRAPH_KEY_TSBEAM : 0u) |
                        (call.bio ? 8u : 0u) | (call.chained ? 4u : 0u) | ((uint64_t)call.use_mask << 1) | (plan.fuse_ln ? 1u : 0u);
   auto it = s->graphs.find(key);
   if (it == s->graphs.end()) {

@@ -37,11 +37,15 @@ struct BeamStepIO { const int* state_src; int32_t* topk_id; float* topk_lp; Beam
 struct SampleStepIO { int32_t* topk_id; float* topk_lp; SampleChainArgs upd; };
 // device-chained timestamp decoding: the same, with the timestamp-rules pick + bookkeeping launch (tsrules.hip) behind it
 struct TsStepIO { int32_t* topk_id; float* topk_lp; TsChainArgs upd; };
+// device-chained beam search under the timestamp rules (tsbeam_chain.cpp): where a step leaves its (unused) top-1 rows, the
+// per-row candidates launch and the per-window bookkeeping launch (tsbeam.hip) behind it
+struct TsBeamStepIO { int32_t* topk_id; float* topk_lp; TsBeamRowsArgs rows; TsBeamUpdateArgs upd; };
 
 // What varies between launches of one plan.  chained: device-chained greedy steps (position and tokens come from the control
 // block); reps > 1: that many consecutive chained steps in one graph; bio: a device-chained beam step; sio: a device-chained
 // sampling step (sample_chain.cpp) -- the sampling update runs behind the logits tail in place of bio's beam update; tio: a
-// device-chained timestamp step (ts_chain.cpp), the timestamp update in that place.  At most one of bio / sio / tio is set.
+// device-chained timestamp step (ts_chain.cpp), the timestamp update in that place; tbio: a step of the beam search under the
+// timestamp rules (tsbeam_chain.cpp), its two launches in that place.  At most one of bio / sio / tio / tbio is set.
 struct StepCall {
   int k = 0, use_mask = 0;
   bool chained = false;
@@ -49,9 +53,11 @@ struct StepCall {
   const BeamStepIO* bio = nullptr;
   const SampleStepIO* sio = nullptr;
   const TsStepIO* tio = nullptr;
+  const TsBeamStepIO* tbio = nullptr;
 };
 constexpr uint64_t GRAPH_KEY_SAMPLE = 16u;   // bit of a captured step's key (launch_step): a sampling step
 constexpr uint64_t GRAPH_KEY_TS = 32u;       // ... a timestamp step
+constexpr uint64_t GRAPH_KEY_TSBEAM = 64u;   // ... a step of the beam search under the timestamp rules
 // Launch one decode step: replay the captured graph for this launch shape (capturing it on first use), or enqueue the kernels
 // eagerly.
 int launch_step(wb_session* s, const StepPlan& plan, const StepCall& call);

@@ -24,6 +24,8 @@ enum KernelClass {
   KC_SAMPLE_UPDATE,
   // timestamp decoding (tsrules.hip): the filter + pick + bookkeeping launch behind a timestamp step's logits tail
   KC_TS_UPDATE,
+  // beam search under the timestamp rules (tsbeam.hip): per-row candidates, per-window bookkeeping
+  KC_TSBEAM_ROWS, KC_TSBEAM_UPDATE,
   KC_COUNT
 };
 void prof_tag(int cls, double algo_bytes);

@@ -5,6 +5,21 @@
 #include "decode.h"
 #include "engine.h"
 
+namespace wb {
+// What a beam search under the timestamp rules leaves on the host: per window the finalized candidates in store order
+// (generated tokens, f64 score, rank) and, per step, the live beams behind it (token, parent beam index, f64 score) with the
+// number newly finished.  Windows that were not active have n_cand = -1 and no steps.
+struct TsBeamResult {
+  int W = 0, depth = 0;
+  std::vector<int> n_cand, best, n_steps;                      // [W]
+  std::vector<std::vector<std::vector<int32_t>>> cand_tokens;  // [W][n_cand]
+  std::vector<std::vector<double>> cand_score, cand_rank;      // [W][n_cand]
+  std::vector<int> tr_n, tr_fin;                               // [depth][W]
+  std::vector<int32_t> tr_tok, tr_par;                         // [depth][W][MAX_BEAMS]
+  std::vector<double> tr_score;                                // [depth][W][MAX_BEAMS]
+};
+}  // namespace wb
+
 struct wb_session {
   wb_model* m = nullptr;
   uint64_t model_uid = 0;       // m->uid at creation: what the pool is keyed by (m may dangle once its model is freed)
@@ -63,6 +78,11 @@ struct wb_session {
   std::vector<uint8_t> ts_sup_host; void* ts_sup_dev_ptr = nullptr;     // what ts_sup holds (same rule as mask_host)
   bool has_suppress = false;
   uint64_t ts_sig = 0;          // what the captured timestamp steps bake in (session_ts_chain)
+  // beam search under the timestamp rules (decode.h: TsBeamUpdateArgs): control block, candidate rows; the finalized
+  // candidates and the trace of the last call (wb_session_last_beams / wb_session_last_beam_trace)
+  wb::DevMem tb_ctl, tb_topk;
+  uint64_t tsbeam_sig = 0;
+  wb::TsBeamResult tb_last;
   std::vector<int> prev_len, prev_win;
   int prev_n = 0, step = 0;
   bool has_mask = false, decode_ready = false;
@@ -130,6 +150,14 @@ int session_sample_chain(wb_session* s, const int32_t* prompt, int prompt_len, c
 int session_ts_chain(wb_session* s, const wb_timestamp_params& tp, const int32_t* prompt, int prompt_len, const uint8_t* active,
                      const int32_t* stream_ids, int eot, int max_depth, int32_t* out_tokens, int32_t row_stride,
                      int32_t* out_lens, double* out_sum, int32_t* out_best);
+// shared by the timestamp chains: the suppress bytes as the kernels' words, and the argument checks
+void pack_suppress(const uint8_t* a, const uint8_t* b, int V, uint32_t* out);
+int check_ts_params(const wb_timestamp_params& tp, int V, int eot, const char* who);
+int check_beam_params(const wb_timestamp_params& tp, const wb_beam_params& bp, int max_beams, int* max_candidates);
+// beam search under the timestamp rules with the candidates and the bookkeeping on the device (tsbeam_chain.cpp)
+int session_tsbeam_chain(wb_session* s, const wb_timestamp_params& tp, const wb_beam_params& bp, const int32_t* prompt, int prompt_len,
+                         const uint8_t* active, int eot, int max_depth, int32_t* out_tokens, int32_t row_stride, int32_t* out_lens,
+                         double* out_score, int32_t* out_n_candidates);
 int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_depth, int mask_until_len, int prompt_len,
                          int32_t* out_tokens, int32_t row_stride, int32_t* out_lens);
 // wb_session_align (align.cpp); drop_last_rows non-null: drop_last per window instead of the scalar, and a row that leaves

@@ -10,7 +10,7 @@
 
 using namespace wb;
 
-namespace {
+namespace wb {
 
 // u8 [V] -> the kernel's words: 4 ids per word, id v in byte (v & 3) of word v >> 2, pad bytes 0
 void pack_suppress(const uint8_t* a, const uint8_t* b, int V, uint32_t* out) {
@@ -38,10 +38,6 @@ int check_ts_params(const wb_timestamp_params& tp, int V, int eot, const char* w
              tp.max_timestamp_index, tp.attempt);
   return WB_OK;
 }
-
-}  // namespace
-
-namespace wb {
 
 // session_sample_chain's structure under the timestamp rules.  Rows are a * best_of + j over the ACTIVE windows in order; the
 // special mask is never applied (use_mask = 0 on every step: a three-token prompt would otherwise mask the timestamps
@@ -367,11 +363,13 @@ int wb_segments_from_tokens(const int32_t* tokens, int32_t n, int32_t tok_timest
   return WB_OK;
 }
 
-int wb_waveform_to_segments(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
-                            const wb_timestamp_params* tp, const uint8_t* suppress, const uint8_t* suppress_first,
-                            const int32_t* prompt, int32_t prompt_len, float* seg_start, float* seg_end_time,
-                            int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap, int32_t* n_segments,
-                            int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens, int32_t* n_windows) {
+// The seek loop of wb_waveform_to_segments; bp non-null: every window by beam search (wb_waveform_to_segments_beam).
+static int waveform_segments_loop(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                                  const wb_timestamp_params* tp, const wb_beam_params* bp, const uint8_t* suppress,
+                                  const uint8_t* suppress_first, const int32_t* prompt, int32_t prompt_len, float* seg_start,
+                                  float* seg_end_time, int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap,
+                                  int32_t* n_segments, int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens,
+                                  int32_t* n_windows) {
   WB_REQUIRE(m && pcm && p && tp && suppress && prompt && seg_start && seg_end_time && seg_tok_begin && seg_tok_end && n_segments &&
                  text_tokens && n_text_tokens, WB_ERR_ARG, "wb_waveform_to_segments: null argument");
   WB_REQUIRE(sample_rate > 0 && tp->seconds_per_timestamp > 0.f && prompt_len >= 1 && p->max_depth >= 0, WB_ERR_ARG,
@@ -382,6 +380,8 @@ int wb_waveform_to_segments(wb_model* m, const float* pcm, int64_t n, int sample
   WB_TRY(check_ts_params(*tp, m->dims.n_vocab, p->tok_end_of_text, "wb_waveform_to_segments"));
   WB_REQUIRE(tp->best_of >= 1 && tp->best_of <= MAX_BEAMS && (tp->temperature > 0.f || tp->best_of == 1), WB_ERR_ARG,
              "wb_waveform_to_segments: best_of %d (temperature %g)", tp->best_of, (double)tp->temperature);
+  int max_cand = 0;
+  if (bp) WB_TRY(check_beam_params(*tp, *bp, MAX_BEAMS, &max_cand));
   for (int i = 0; i < prompt_len; i++)
     WB_REQUIRE(prompt[i] >= 0 && prompt[i] < m->dims.n_vocab, WB_ERR_ARG, "prompt token %d out of range", prompt[i]);
   const int64_t wlen = wb_max_waveform_samples(m->max_mel_frames() - p->padding);
@@ -398,14 +398,16 @@ int wb_waveform_to_segments(wb_model* m, const float* pcm, int64_t n, int sample
     wb_timestamp_params wtp = *tp;
     if (wtp.max_timestamp_index < 0 || wtp.max_timestamp_index > win_index) wtp.max_timestamp_index = win_index;
     wb_session* s = nullptr;
-    int rc = session_create(m, 1, std::max(1, tp->best_of), p->padding, &s);
+    int rc = session_create(m, 1, bp ? bp->beam_size : std::max(1, tp->best_of), p->padding, &s);
     int32_t rlen = 0;
     if (rc == WB_OK) {
       s->sample_rate = (double)sample_rate;
       rc = session_encode_pcm(s, pcm, n, &seek, &len, false);
       if (rc == WB_OK) rc = wb_session_set_suppress(s, suppress, suppress_first);
-      if (rc == WB_OK) rc = wb_session_decode_timestamps(s, p, &wtp, prompt, prompt_len, nullptr, nullptr, row.data(), stride, &rlen,
-                                                         nullptr, nullptr);
+      if (rc == WB_OK)
+        rc = bp ? wb_session_decode_timestamps_beam(s, p, &wtp, bp, prompt, prompt_len, nullptr, row.data(), stride, &rlen, nullptr, nullptr)
+                : wb_session_decode_timestamps(s, p, &wtp, prompt, prompt_len, nullptr, nullptr, row.data(), stride, &rlen, nullptr,
+                                               nullptr);
       wb_session_free(s);
     }
     WB_TRY(rc);
@@ -434,6 +436,28 @@ int wb_waveform_to_segments(wb_model* m, const float* pcm, int64_t n, int sample
   *n_segments = ns; *n_text_tokens = nt;
   if (n_windows) *n_windows = nw;
   return WB_OK;
+}
+
+int wb_waveform_to_segments(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                            const wb_timestamp_params* tp, const uint8_t* suppress, const uint8_t* suppress_first,
+                            const int32_t* prompt, int32_t prompt_len, float* seg_start, float* seg_end_time,
+                            int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap, int32_t* n_segments,
+                            int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens, int32_t* n_windows) {
+  return waveform_segments_loop(m, pcm, n, sample_rate, p, tp, nullptr, suppress, suppress_first, prompt, prompt_len, seg_start,
+                                seg_end_time, seg_tok_begin, seg_tok_end, seg_cap, n_segments, text_tokens, text_cap, n_text_tokens,
+                                n_windows);
+}
+
+int wb_waveform_to_segments_beam(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                                 const wb_timestamp_params* tp, const wb_beam_params* bp, const uint8_t* suppress,
+                                 const uint8_t* suppress_first, const int32_t* prompt, int32_t prompt_len, float* seg_start,
+                                 float* seg_end_time, int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap,
+                                 int32_t* n_segments, int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens,
+                                 int32_t* n_windows) {
+  WB_REQUIRE(bp, WB_ERR_ARG, "wb_waveform_to_segments_beam: null argument");
+  return waveform_segments_loop(m, pcm, n, sample_rate, p, tp, bp, suppress, suppress_first, prompt, prompt_len, seg_start,
+                                seg_end_time, seg_tok_begin, seg_tok_end, seg_cap, n_segments, text_tokens, text_cap, n_text_tokens,
+                                n_windows);
 }
 
 }  // extern "C"

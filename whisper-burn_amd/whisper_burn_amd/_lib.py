@@ -48,6 +48,13 @@ class WbTimestampParams(C.Structure):
                 ("best_of", C.c_int32), ("seed", C.c_uint64), ("attempt", C.c_int32)]
 
 
+class WbBeamParams(C.Structure):
+    _fields_ = [("beam_size", C.c_int32), ("patience", C.c_float), ("length_penalty", C.c_float)]
+
+
+# wb_tsbeam_logits_fn (include/whisper_hip.h)
+TSBEAM_LOGITS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_float_p)
+
 # wb_ratio_fn (include/whisper_hip.h)
 RATIO_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, c_int32_p, C.c_int32)
 
@@ -193,6 +200,27 @@ SIGNATURES = {
                                           C.POINTER(WbTimestampParams), c_uint8_p, c_uint8_p, c_int32_p, C.c_int32, c_float_p,
                                           c_float_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p, C.c_int64,
                                           c_int64_p, c_int32_p]),
+    "wb_beam_params_default": (None, [C.POINTER(WbBeamParams)]),
+    "wb_session_decode_timestamps_beam": (C.c_int, [C.c_void_p, C.POINTER(WbDecodeParams), C.POINTER(WbTimestampParams),
+                                                    C.POINTER(WbBeamParams), c_int32_p, C.c_int32, c_uint8_p, c_int32_p,
+                                                    C.c_int32, c_int32_p, c_double_p, c_int32_p]),
+    "wb_session_last_beams": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, c_int32_p, c_double_p, c_double_p,
+                                        c_int32_p]),
+    "wb_session_last_beam_trace": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                             c_double_p]),
+    "wb_timestamp_beam_rows": (C.c_int, [C.c_int, c_float_p, C.c_int32, C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                         C.c_int32, C.c_int32, c_int32_p, c_float_p, c_int32_p, c_int32_p, c_float_p,
+                                         c_int32_p]),
+    "wb_timestamp_beam_search_device": (C.c_int, [C.c_int, C.POINTER(WbTimestampParams), C.POINTER(WbBeamParams), C.c_int32,
+                                                  C.c_int32, c_uint8_p, c_uint8_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, c_int32_p, C.c_int32, c_int32_p, c_double_p, c_double_p,
+                                                  c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                                  c_int32_p, c_double_p]),
+    "wb_waveform_to_segments_beam": (C.c_int, [C.c_void_p, c_float_p, C.c_int64, C.c_int, C.POINTER(WbDecodeParams),
+                                               C.POINTER(WbTimestampParams), C.POINTER(WbBeamParams), c_uint8_p, c_uint8_p,
+                                               c_int32_p, C.c_int32, c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int32,
+                                               c_int32_p, c_int32_p, C.c_int64, c_int64_p, c_int32_p]),
     "wb_first_repetition_end": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_repetition_period": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_find_repeated_tokens_index": (C.c_int, [c_int32_p, C.c_int64, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),

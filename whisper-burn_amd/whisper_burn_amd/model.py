@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import WbDecodeParams, WbDims, WbError, WbFallbackParams, WbSampleParams, WbTimestampParams, check
+from ._lib import WbBeamParams, WbDecodeParams, WbDims, WbError, WbFallbackParams, WbSampleParams, WbTimestampParams, check
 from .tokens import SpecialTokens
 
 WB_F32, WB_BF16 = 0, 1
@@ -141,6 +141,103 @@ def TimestampParams(timestamp_begin: int = 0, n_timestamps: int = 0, max_initial
     return p
 
 
+def BeamParams(beam_size: int = 5, patience: float = 1.0, length_penalty: float = -1.0) -> WbBeamParams:
+    """wb_beam_params: beam search under the timestamp rules -- beam_size live beams, a finished store of
+    round(beam_size * patience) candidates, ranking by score / n_text (length_penalty < 0) or Google NMT's penalty."""
+    p = WbBeamParams()
+    _lib.load().wb_beam_params_default(C.byref(p))
+    p.beam_size, p.patience, p.length_penalty = int(beam_size), patience, length_penalty
+    return p
+
+
+BEAM_STORE_CAP = 16     # most finalized candidates of a window (wb_session_last_beams)
+
+
+def _beams_out(W: int, depth: int):
+    cap, stride = BEAM_STORE_CAP, max(depth, 1)
+    return (np.zeros((W, cap, stride), dtype=np.int32), np.zeros((W, cap), dtype=np.int32), np.zeros((W, cap), dtype=np.float64),
+            np.zeros((W, cap), dtype=np.float64), np.zeros(W, dtype=np.int32))
+
+
+def _beams_list(toks, lens, scores, ranks, n):
+    return [None if n[w] < 0 else [dict(tokens=toks[w, i, :lens[w, i]].tolist(), score=float(scores[w, i]), rank=float(ranks[w, i]))
+                                   for i in range(n[w])] for w in range(len(n))]
+
+
+def _trace_out(W: int, depth: int):
+    T = max(depth, 1)
+    return (np.zeros(W, dtype=np.int32), np.zeros((T, W), dtype=np.int32), np.zeros((T, W), dtype=np.int32),
+            np.zeros((T, W, 8), dtype=np.int32), np.zeros((T, W, 8), dtype=np.int32), np.zeros((T, W, 8), dtype=np.float64))
+
+
+def _trace_list(n_steps, n_live, n_fin, toks, pars, scores):
+    return [[dict(finished=int(n_fin[t, w]), beams=[(int(toks[t, w, q]), int(pars[t, w, q]), float(scores[t, w, q]))
+                                                     for q in range(n_live[t, w])]) for t in range(n_steps[w])]
+            for w in range(len(n_steps))]
+
+
+def timestamp_beam_rows(logits, tp: WbTimestampParams, n_gen, prev1, prev2, last_ts, eot: int, k: int, V: Optional[int] = None,
+                        suppress=None, suppress_first=None, device: int = 0):
+    """The candidates of the beam search's rows kernel alone (wb_timestamp_beam_rows, a test hook): timestamp_rows' inputs at
+    temperature 0 plus k.  Returns (ids [R, k], logprobs [R, k], count [R], forced [R], stats [R, 2], error word); entries
+    past a row's count keep their fill (-1 / nan)."""
+    x = _f32(logits)
+    R, ld = x.shape
+    V = ld if V is None else V
+    cols = [_i32(c) for c in (n_gen, prev1, prev2, last_ts)]
+    assert all(c.shape == (R,) for c in cols)
+    sup, sup1 = _u8v(suppress, V), _u8v(suppress_first, V)
+    kk = max(int(k), 1)
+    ids = np.full((R, kk), -1, dtype=np.int32)
+    lp = np.full((R, kk), np.nan, dtype=np.float32)
+    count = np.full(R, -1, dtype=np.int32)
+    forced = np.full(R, -1, dtype=np.int32)
+    stats = np.full((R, 2), np.nan, dtype=np.float32)
+    err = np.full(1, -1, dtype=np.int32)
+    check(_lib.load().wb_timestamp_beam_rows(device, _fp(x), R, ld, V, _u8p(sup), _u8p(sup1), tp.tok_timestamp_begin, tp.n_timestamps,
+                                             tp.max_initial_timestamp_index, tp.max_timestamp_index, *[_ip(c) for c in cols],
+                                             int(eot), int(k), _ip(ids), _fp(lp), _ip(count), _ip(forced), _fp(stats), _ip(err)))
+    return ids, lp, count, forced, stats, int(err[0])
+
+
+def timestamp_beam_search_device(fill, tp: WbTimestampParams, bp: WbBeamParams, n_windows: int, V: int, eot: int, max_depth: int,
+                                 suppress=None, suppress_first=None, device: int = 0):
+    """Both kernels of the beam search under the timestamp rules without a model (wb_timestamp_beam_search_device, a test
+    hook).  fill(step, window [n], beam [n], token [n], parent [n]) -> logits [n, V] of the live rows.  Returns (beams, best,
+    trace) as Session.last_beams / the index of the returned candidate per window / Session.last_beam_trace."""
+    W = int(n_windows)
+    error = []
+
+    def cb(_user, step, n, win, beam, tok, par, out):
+        try:
+            arr = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy()
+            x = np.ascontiguousarray(fill(int(step), arr(win), arr(beam), arr(tok), arr(par)), dtype=np.float32)
+            assert x.shape == (n, V), x.shape
+            np.ctypeslib.as_array(out, shape=(n, V))[:] = x
+            return 0
+        except Exception as e:  # noqa: BLE001 - reported through the status
+            error.append(e)
+            return -1
+
+    fn = _lib.TSBEAM_LOGITS_FN(cb)
+    sup, sup1 = _u8v(suppress, V), _u8v(suppress_first, V)
+    toks, lens, scores, ranks, n = _beams_out(W, max_depth)
+    best = np.zeros(W, dtype=np.int32)
+    tr = _trace_out(W, max_depth)
+    try:
+        check(_lib.load().wb_timestamp_beam_search_device(device, C.byref(tp), C.byref(bp), W, V, _u8p(sup), _u8p(sup1), int(eot),
+                                                          int(max_depth), C.cast(fn, C.c_void_p), None, _ip(toks), toks.shape[2],
+                                                          _ip(lens), scores.ctypes.data_as(_lib.c_double_p),
+                                                          ranks.ctypes.data_as(_lib.c_double_p), _ip(n), _ip(best), _ip(tr[0]),
+                                                          _ip(tr[1]), _ip(tr[2]), _ip(tr[3]), _ip(tr[4]),
+                                                          tr[5].ctypes.data_as(_lib.c_double_p)))
+    except WbError:
+        if error:
+            raise error[0]
+        raise
+    return _beams_list(toks, lens, scores, ranks, n), best.tolist(), _trace_list(*tr)
+
+
 def _u8v(a, V: int) -> Optional[np.ndarray]:
     if a is None:
         return None
@@ -187,10 +284,12 @@ def segments_from_tokens(tokens, tp: WbTimestampParams, eot: int, window_index: 
 
 
 def waveform_to_segments(whisper: "Whisper", st: SpecialTokens, waveform, sample_rate: int = 16000, params=None,
-                         timestamps: Optional[WbTimestampParams] = None, suppress=None, suppress_first=None, prompt=None):
+                         timestamps: Optional[WbTimestampParams] = None, suppress=None, suppress_first=None, prompt=None,
+                         beam: Optional[WbBeamParams] = None):
     """Long-form transcription by timestamps (wb_waveform_to_segments): the window moves by the last decoded timestamp.
     Returns (segments, tokens, n_windows): segments = dict(start, end, tokens) with absolute seconds and the segment's
-    non-timestamp tokens; tokens = their concatenation."""
+    non-timestamp tokens; tokens = their concatenation.  beam: BeamParams -- every window by beam search under the rules
+    (wb_waveform_to_segments_beam); None: greedy / best-of-n as `timestamps` says."""
     from .tokens import default_suppress
     wav = _f32(waveform).reshape(-1)
     p = params if params is not None else decode_params(st)
@@ -211,9 +310,13 @@ def waveform_to_segments(whisper: "Whisper", st: SpecialTokens, waveform, sample
     b, e = np.zeros(seg_cap, dtype=np.int32), np.zeros(seg_cap, dtype=np.int32)
     text = np.zeros(text_cap, dtype=np.int32)
     ns, nw, nt = C.c_int32(0), C.c_int32(0), C.c_int64(0)
-    check(_lib.load().wb_waveform_to_segments(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p), C.byref(tp), _u8p(sup),
-                                              _u8p(sup1), _ip(pr), len(pr), _fp(t0), _fp(t1), _ip(b), _ip(e), seg_cap,
-                                              C.byref(ns), _ip(text), text_cap, C.byref(nt), C.byref(nw)))
+    tail = (_u8p(sup), _u8p(sup1), _ip(pr), len(pr), _fp(t0), _fp(t1), _ip(b), _ip(e), seg_cap, C.byref(ns), _ip(text), text_cap,
+            C.byref(nt), C.byref(nw))
+    if beam is None:
+        check(_lib.load().wb_waveform_to_segments(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p), C.byref(tp), *tail))
+    else:
+        check(_lib.load().wb_waveform_to_segments_beam(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p), C.byref(tp),
+                                                       C.byref(beam), *tail))
     toks = text[:nt.value].tolist()
     segs = [dict(start=float(t0[i]), end=float(t1[i]), tokens=toks[b[i]:e[i]]) for i in range(ns.value)]
     return segs, toks, int(nw.value)
@@ -947,6 +1050,42 @@ class Session:
                                                        _ip(sid) if sid is not None else None, _ip(toks), toks.shape[1],
                                                        _ip(lens), sums.ctypes.data_as(_lib.c_double_p), _ip(best)))
         return [toks[i, :lens[i]].tolist() for i in range(W)], sums, best
+
+    def decode_timestamps_beam(self, params: WbDecodeParams, timestamps: WbTimestampParams, beam: WbBeamParams, prompt=None,
+                               active=None, out_tokens: Optional[np.ndarray] = None, out_lens: Optional[np.ndarray] = None):
+        """Beam search under the timestamp rules (wb_session_decode_timestamps_beam), on a fresh or rewound session after
+        set_suppress.  prompt / active / out_tokens / out_lens as decode_timestamps.  Returns (rows, score [W] f64 -- the
+        best candidate's cumulative log-prob, nan for inactive windows --, n_candidates [W], -1 for inactive windows)."""
+        W = self.n_windows
+        pr = _i32([params.tok_start_of_transcript, params.tok_language, params.tok_transcribe] if prompt is None else list(prompt))
+        stride = len(pr) + params.max_depth + 4
+        toks = out_tokens if out_tokens is not None else np.zeros((W, stride), dtype=np.int32)
+        lens = out_lens if out_lens is not None else np.zeros(W, dtype=np.int32)
+        assert toks.dtype == np.int32 and toks.flags.c_contiguous and toks.shape[0] == W and lens.dtype == np.int32
+        act = np.ascontiguousarray(active, dtype=np.uint8) if active is not None else None
+        score = np.full(W, np.nan, dtype=np.float64)
+        ncand = np.full(W, -1, dtype=np.int32)
+        check(_lib.load().wb_session_decode_timestamps_beam(self._h, C.byref(params), C.byref(timestamps), C.byref(beam), _ip(pr),
+                                                            len(pr), _u8p(act), _ip(toks), toks.shape[1], _ip(lens),
+                                                            score.ctypes.data_as(_lib.c_double_p), _ip(ncand)))
+        return [toks[i, :lens[i]].tolist() for i in range(W)], score, ncand
+
+    def last_beams(self, max_depth: int):
+        """Every finalized candidate of the last decode_timestamps_beam (wb_session_last_beams), in store order: per window a
+        list of dict(tokens -- generated, no prompt --, score, rank); None for the windows that were not active."""
+        toks, lens, scores, ranks, n = _beams_out(self.n_windows, max_depth)
+        check(_lib.load().wb_session_last_beams(self._h, toks.shape[1], _ip(toks), toks.shape[2], _ip(lens),
+                                                scores.ctypes.data_as(_lib.c_double_p), ranks.ctypes.data_as(_lib.c_double_p), _ip(n)))
+        return _beams_list(toks, lens, scores, ranks, n)
+
+    def last_beam_trace(self, max_depth: int):
+        """The trace of the last decode_timestamps_beam (wb_session_last_beam_trace): per window a list of steps, each
+        dict(finished = candidates newly finished in the step, beams = [(token, parent beam index, f64 score)] of the live
+        beams behind it)."""
+        tr = _trace_out(self.n_windows, max_depth)
+        check(_lib.load().wb_session_last_beam_trace(self._h, tr[1].shape[0], _ip(tr[0]), _ip(tr[1]), _ip(tr[2]), _ip(tr[3]),
+                                                     _ip(tr[4]), tr[5].ctypes.data_as(_lib.c_double_p)))
+        return _trace_list(*tr)
 
     def last_samples(self, best_of: int, max_depth: int) -> List[List[Optional[List[int]]]]:
         """Every sample of the last decode_sample (wb_session_last_samples): [W][best_of] lists of generated tokens (without

@@ -31,6 +31,9 @@ speech).
 `--segments PATH` decodes WITH timestamp tokens (wb_waveform_to_segments: Whisper's timestamp rules on the device, the
 window moves by the last decoded timestamp) and writes one JSON line per segment, {"start", "end", "text", "tokens"} with
 times in seconds; the transcript is then the segments' text.  Not together with --fallback, --token-times or --scores.
+With it, `--beam-size N` (1 .. 7) decodes every window by beam search under the timestamp rules
+(wb_waveform_to_segments_beam: Whisper's BeamSearchDecoder on the device), optionally with `--patience X` (>= 1, default 1)
+and `--length-penalty A` (default: rank by average log-prob); the three flags are rejected without `--segments`.
 
 One addition: with `WHISPER_HIP_RESAMPLE=1` in the environment a mono WAV of another sample rate (the bundled
 22 050 Hz audio.wav, which the reference sends through `sox`, README.md:69-74) is resampled to 16 kHz on the GPU
@@ -56,7 +59,7 @@ def main(argv=None) -> int:
     segments_file = None
     extra = argv[5:]
     usage = (f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference] "
-             f"[--token-times PATH] [--scores PATH] [--segments PATH] [--fallback [--temperatures T0,T1,..] [--best-of N] [--seed N] "
+             f"[--token-times PATH] [--scores PATH] [--segments PATH [--beam-size N [--patience X] [--length-penalty A]]] [--fallback [--temperatures T0,T1,..] [--best-of N] [--seed N] "
              f"[--logprob-threshold X] [--no-speech-threshold X] [--compression-ratio-threshold X]]")
     fallback = False
     fb = {}                                     # keyword arguments of FallbackParams given on the command line
@@ -64,8 +67,18 @@ def main(argv=None) -> int:
                "--seed": ("seed", int), "--logprob-threshold": ("logprob_threshold", float),
                "--no-speech-threshold": ("no_speech_threshold", float),
                "--compression-ratio-threshold": ("compression_ratio_threshold", float)}
+    beam = {}                                   # keyword arguments of BeamParams given on the command line
+    beam_opts = {"--beam-size": ("beam_size", int), "--patience": ("patience", float), "--length-penalty": ("length_penalty", float)}
     while extra:                                # (other trailing arguments are ignored, as before)
-        if extra[0] == "--fallback":
+        if extra[0] in beam_opts:
+            key, conv = beam_opts[extra[0]]
+            try:
+                beam[key] = conv(extra[1])
+            except (IndexError, ValueError):
+                print(usage, file=sys.stderr)
+                return 1
+            extra = extra[2:]
+        elif extra[0] == "--fallback":
             fallback = True
             extra = extra[1:]
         elif extra[0] in fb_opts:
@@ -93,6 +106,10 @@ def main(argv=None) -> int:
             extra = extra[1:]
     if fb and not fallback:
         print("The fallback options (--temperatures, --best-of, --seed, --*-threshold) need --fallback\n" + usage, file=sys.stderr)
+        return 1
+    if beam and (segments_file is None or "beam_size" not in beam):
+        print("--beam-size / --patience / --length-penalty (beam search under the timestamp rules) need --segments and --beam-size\n"
+              + usage, file=sys.stderr)
         return 1
     if fallback and times_file is not None:
         print("--token-times is not available together with --fallback\n" + usage, file=sys.stderr)
@@ -173,7 +190,8 @@ def main(argv=None) -> int:
             if st.n_timestamps == 0:
                 raise ValueError("the tokenizer has no timestamp tokens (<|0.00|> ...)")
             sup, sup_first = default_suppress(st, bpe)
-            segments, _tokens, _ = wb.waveform_to_segments(whisper, st, waveform, sample_rate, suppress=sup, suppress_first=sup_first)
+            segments, _tokens, _ = wb.waveform_to_segments(whisper, st, waveform, sample_rate, suppress=sup, suppress_first=sup_first,
+                                                           beam=wb.BeamParams(**beam) if beam else None)
             text = bpe.decode(_tokens, True)
         elif fallback:
             st = bpe.special_tokens(lang)
