@@ -730,6 +730,55 @@ int wb_waveform_to_segments_beam(wb_model* m, const float* pcm, int64_t n, int s
                                  int32_t* n_segments, int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens,
                                  int32_t* n_windows);
 
+/* ---- prompt prefill by one pass, and the seek loop conditioned on previous text (an extension) -----------------------
+ * Every decode entry point feeds its prompt's first P - 1 tokens to the self-KV cache by P - 1 decode steps (one host round
+ * trip each).  Prefill mode 1 replaces them by ONE teacher-forced pass over all prompt positions on the matrix cores that
+ * writes the paged cache and the position tables directly; the chained steps continue from there.  The pass leaves the
+ * session where the steps leave it, up to rounding (exact-f32 MFMA GEMMs instead of f32 GEMVs).
+ * mode: 0 (default; a pooled session starts there) steps, 1 the pass.  It applies to wb_session_decode,
+ * wb_session_decode_prompt, wb_session_decode_sample, wb_session_decode_timestamps and wb_session_decode_timestamps_beam on a
+ * fresh or rewound session.  WHISPER_HIP_PREFILL_PASS=0 forces steps everywhere.  Any other mode -> WB_ERR_ARG. */
+int wb_session_set_prefill(wb_session* s, int mode);
+/* The pass alone, on a fresh or rewound session: equivalent to the n calls wb_session_step(tokens[t], parent = t == 0 ? -1 :
+ * a, window = the a-th active window, k = 0), t = 0 .. n - 1, with one synchronisation at its end; wb_session_step continues
+ * behind it with parent = a.  active: u8 [W] or NULL (all).  n == 0 is a no-op.  A session that is not at step 0 ->
+ * WB_ERR_STATE; a token outside the vocabulary -> WB_ERR_ARG; n >= the cache's capacity (min(n_text_ctx, 448) unless a decode
+ * call reserved less) -> WB_ERR_SHAPE; nothing is launched in any of these. */
+int wb_session_prefill(wb_session* s, const int32_t* tokens, int32_t n, const uint8_t* active);
+/* Test hook: the store kernel of the pass alone on caller arrays in host memory.  qkv [nA * n][ld] (row a * n + p; ld >= 3 d,
+ * d and ld multiples of 4); Kc / Vc [Lmax * S][d] and tabs [2][S][Lmax] are read AND written: the kernel's writes land in
+ * the caller's contents.  It copies columns [d, 2d) / [2d, 3d) of row a * n + p to row p * S + a of Kc / Vc and sets
+ * tabs[(n - 1) & 1][a][p] = p * S + a; nothing else.  `device` only hosts the buffers. */
+int wb_prefill_store(int device, const float* qkv, int32_t nA, int32_t n, int32_t d, int32_t ld, int32_t S, int32_t Lmax,
+                     float* Kc, float* Vc, int32_t* tabs);
+/* Test hook: the cached self-attention rows of live slot `slot` (a row of the last step or prefill) in decoder layer `layer`,
+ * positions [0, n_pos), read through the slot's current position table: K (pre-scaled by (d / heads)^-0.25) and V, [n_pos][d]. */
+int wb_session_self_kv(wb_session* s, int32_t layer, int32_t slot, int32_t n_pos, float* K, float* V);
+/* wb_waveform_to_segments_beam (bp NULL: wb_waveform_to_segments, greedy or best-of-n as tp says) with every window's prompt
+ * conditioned on the text before it -- Whisper transcribe()'s condition_on_previous_text / initial_prompt.  The rule:
+ *   - `history` starts as initial_prompt [n_initial_prompt].
+ *   - The prompt of a window is [tok_start_of_prev] + the last min(cap, len(history)) tokens of history + prompt, with
+ *     cap = max_prompt_tokens < 0 ? n_text_ctx / 2 - 1 : max_prompt_tokens; when that history section is empty the prompt is
+ *     `prompt` alone, without tok_start_of_prev.
+ *   - After a window, the generated tokens its segments cover -- gen[seg_begin[0], seg_end[k - 1]): timestamps included,
+ *     end-of-text excluded, nothing when it has no segment -- are appended to history.  Tokens behind the last closed pair
+ *     are not appended (the next window decodes them again).
+ *   - Then history is emptied if condition_on_previous_text == 0 or tp->temperature > 0.5 (so with conditioning off the
+ *     initial prompt reaches the first window only).
+ * A window whose prompt carries a history section is decoded in prefill mode 1, any other in mode 0: with conditioning off
+ * and no initial prompt the result is wb_waveform_to_segments' bit for bit.  max_depth is clamped by the decode calls as
+ * always (capacity - (prompt length - 1)).  win_seek / win_prompt_len [win_cap] (may be NULL): per window its first sample
+ * and the length of its prompt.  tok_start_of_prev or an initial_prompt token outside [0, n_vocab) -> WB_ERR_ARG before
+ * anything is encoded. */
+int wb_waveform_to_segments_conditioned(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                                        const wb_timestamp_params* tp, const wb_beam_params* bp, const uint8_t* suppress,
+                                        const uint8_t* suppress_first, const int32_t* prompt, int32_t prompt_len,
+                                        int32_t tok_start_of_prev, int32_t condition_on_previous_text, int32_t max_prompt_tokens,
+                                        const int32_t* initial_prompt, int32_t n_initial_prompt, float* seg_start,
+                                        float* seg_end_time, int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap,
+                                        int32_t* n_segments, int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens,
+                                        int32_t* n_windows, int64_t* win_seek, int32_t* win_prompt_len, int32_t win_cap);
+
 /* The reference's retired greedy decoder kept its repetition detectors (transcribe.rs:385-447, dead code there):
  *   wb_first_repetition_end        :385-393   (period > n, a usize underflow panic there -> WB_ERR_ARG)
  *   wb_repetition_period           :395-417   returns the period, 0 for None

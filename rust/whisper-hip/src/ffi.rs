@@ -282,6 +282,22 @@ extern "C" {
                                         seg_end_time: *mut c_float, seg_tok_begin: *mut i32, seg_tok_end: *mut i32,
                                         seg_cap: i32, n_segments: *mut i32, text_tokens: *mut i32, text_cap: i64,
                                         n_text_tokens: *mut i64, n_windows: *mut i32) -> c_int;
+    pub fn wb_session_set_prefill(s: *mut wb_session, mode: c_int) -> c_int;
+    pub fn wb_session_prefill(s: *mut wb_session, tokens: *const i32, n: i32, active: *const u8) -> c_int;
+    pub fn wb_prefill_store(device: c_int, qkv: *const c_float, nA: i32, n: i32, d: i32, ld: i32, S: i32, Lmax: i32,
+                            Kc: *mut c_float, Vc: *mut c_float, tabs: *mut i32) -> c_int;
+    pub fn wb_session_self_kv(s: *mut wb_session, layer: i32, slot: i32, n_pos: i32, K: *mut c_float,
+                              V: *mut c_float) -> c_int;
+    pub fn wb_waveform_to_segments_conditioned(m: *mut wb_model, pcm: *const c_float, n: i64, sample_rate: c_int,
+                                               p: *const wb_decode_params, tp: *const wb_timestamp_params,
+                                               bp: *const wb_beam_params, suppress: *const u8, suppress_first: *const u8,
+                                               prompt: *const i32, prompt_len: i32, tok_start_of_prev: i32,
+                                               condition_on_previous_text: i32, max_prompt_tokens: i32,
+                                               initial_prompt: *const i32, n_initial_prompt: i32, seg_start: *mut c_float,
+                                               seg_end_time: *mut c_float, seg_tok_begin: *mut i32, seg_tok_end: *mut i32,
+                                               seg_cap: i32, n_segments: *mut i32, text_tokens: *mut i32, text_cap: i64,
+                                               n_text_tokens: *mut i64, n_windows: *mut i32, win_seek: *mut i64,
+                                               win_prompt_len: *mut i32, win_cap: i32) -> c_int;
     pub fn wb_fallback_params_default(p: *mut wb_fallback_params);
     pub fn wb_fallback_decide(fp: *const wb_fallback_params, avg_logprob: c_float, no_speech_prob: c_float,
                               ratio: c_float) -> c_int;

@@ -71,12 +71,11 @@ int session_beam_chain(wb_session* s, const int32_t* prompt, int P, int k, int e
   WB_HIP(hipSetDevice(m->device));
   hipStream_t st = s->st;
   const StepLayout& L = s->lay;
-  {  // prefill: all prompt tokens but the last only feed the KV cache (beam_search_windows does the same)
-    std::vector<int32_t> tok(W), par(W), win(W);
-    for (int t = 0; t < P - 1; t++) {
-      for (int w = 0; w < W; w++) { tok[w] = prompt[t]; par[w] = t == 0 ? -1 : w; win[w] = w; }
-      WB_TRY(wb_session_step(s, tok.data(), par.data(), win.data(), W, 0, 0, nullptr, nullptr));
-    }
+  {  // prefill: all prompt tokens but the last only feed the KV cache (beam_search_windows does the same) -- P - 1 steps, or one
+     // pass when the session's prefill mode asks for it (prefill.cpp)
+    std::vector<int> win(W);
+    for (int w = 0; w < W; w++) win[w] = w;
+    WB_TRY(session_prefill_prompt(s, prompt, P, win.data(), W));
   }
   const BeamChainLayout bl = make_beam_layout(W, std::max(max_depth, 0));
   WB_TRY(s->bc_ctl.ensure((size_t)bl.total_ints * 4));

@@ -435,6 +435,12 @@ int session_greedy_chain(wb_session* s, const int32_t* prompt, int eot, int max_
   }
   // prompt positions the persistent launch runs itself (a fresh session; WHISPER_HIP_PERSIST_PREFILL=0: host-driven prefill)
   int n_forced = 0;
+  if (s->step == 0 && s->prefill_mode == 1 && sw::prefill_pass() && prompt_len > 1) {
+    // one-pass prompt prefill (prefill.cpp): the session is "prefilled" afterwards, so the launch below forces nothing
+    std::vector<int> win(W);
+    for (int w = 0; w < W; w++) win[w] = w;
+    WB_TRY(session_prefill(s, prompt, prompt_len - 1, win.data(), W));
+  }
   if (persist && sw::persist_prefill() && s->step == 0 && n_forced_max <= PS_MAX_FORCED && s->has_mask) n_forced = n_forced_max;
   if (n_forced == 0) WB_TRY(host_prefill());
   WB_TRY(seed_ctl(!persist));

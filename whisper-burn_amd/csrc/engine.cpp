@@ -398,8 +398,11 @@ int run_encoder_unguarded(wb_model* m, hipStream_t st, Workspace& ws, const MelB
 // the workspace's residual stream ws.x (scratch: ws.h / qkv / att / hm, sized by the caller).  sg: n masked self-attention
 // segments followed by n cross-attention segments; the pre-scaled cross K|V of layer i at ckv + i * layer_stride, rows of
 // ldkv.  Shared by the stateless decoder and the scoring pass: one wiring of the column scales and the residual adds.
+// after_qkv (the prompt prefill): runs behind every layer's QKV GEMM with (layer, qkv [rows][3d]); stop_after_last_qkv: the
+// last layer ends there -- its attention, cross-attention and MLP produce nothing such a caller reads.
 static int decoder_blocks(wb_model* m, hipStream_t st, Workspace& ws, int rows, int n, int L, const AttnSeg* sg,
-                          const float* ckv, int64_t layer_stride, int ldkv) {
+                          const float* ckv, int64_t layer_stride, int ldkv,
+                          const std::function<int(int, const float*)>& after_qkv = {}, bool stop_after_last_qkv = false) {
   const int d = m->dims.n_text_state, H = m->dims.n_text_head, NL = m->dims.n_text_layer;
   float *x = ws.x.as<float>(), *h = ws.h.as<float>(), *qkv = ws.qkv.as<float>(), *att = ws.att.as<float>(),
         *hm = ws.hm.as<float>();
@@ -410,6 +413,8 @@ static int decoder_blocks(wb_model* m, hipStream_t st, Workspace& ws, int rows, 
     g = linear_args(h, rows, b.qkv, qkv);
     g.col_scale = m->qk_scale; g.col_scale_period = 3 * d; g.col_scale_width = 2 * d;
     WB_TRY(gemm(m, st, g, &b.qkv));
+    if (after_qkv) WB_TRY(after_qkv(i, qkv));
+    if (stop_after_last_qkv && i == NL - 1) break;
     launch_attention_f32(st, qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, sg, n, L, H, 1.0f, 1);
     g = linear_args(att, rows, b.out, x);
     g.residual = x; g.ldr = d;
@@ -665,6 +670,41 @@ int run_score(wb_model* m, hipStream_t st, Workspace& ws, ScoreJob& J) {
   WB_HIP(hipGetLastError());
   J.result_host.resize((size_t)rows + (size_t)n * NP);       // logprob [rows] | probe_lp [n NP]
   WB_HIP(hipMemcpyAsync(J.result_host.data(), a.logprob, J.result_host.size() * 4, hipMemcpyDeviceToHost, st));
+  return WB_OK;
+}
+
+// The prompt prefill: run_score's layers over nA rows of the same n tokens, each layer's K / V stored into the paged cache
+// behind its QKV GEMM (prefill.hip), ended at the last layer's QKV.  Exact f32 (no guarded scope is open), no logits.
+int run_prefill(wb_model* m, hipStream_t st, Workspace& ws, PrefillJob& J) {
+  const wb_dims& D = m->dims;
+  const int d = D.n_text_state, H = D.n_text_head;
+  const int nA = J.nA, n = J.n, rows = nA * n;
+  WB_REQUIRE(nA > 0 && n > 0 && d == 64 * H, WB_ERR_SHAPE, "prefill: unsupported shape");
+  J.segs_host.resize(2 * nA);
+  J.tok_host.resize((size_t)rows);
+  for (int a = 0; a < nA; a++) {
+    J.segs_host[a] = AttnSeg{a * n, n, a * n, n};                        // masked self-attention
+    J.segs_host[nA + a] = AttnSeg{a * n, n, J.kv_row0[a], J.C[a]};       // cross-attention
+    std::copy(J.tokens.begin(), J.tokens.end(), J.tok_host.begin() + (size_t)a * n);
+  }
+  WB_TRY(upload(st, ws.segs, J.segs_host.data(), J.segs_host.size() * sizeof(AttnSeg)));
+  ws.enc_T.clear();                   // (ws.segs no longer holds the encoder's segments)
+  WB_TRY(upload(st, ws.score.i32, J.tok_host.data(), J.tok_host.size() * 4));   // (the scoring pass's token buffer: one owner at a time)
+  WB_TRY(ws.x.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.h.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.qkv.ensure((size_t)rows * 3 * d * 4));
+  WB_TRY(ws.att.ensure((size_t)rows * d * 4));
+  WB_TRY(ws.hm.ensure((size_t)rows * 4 * d * 4));
+  launch_embed(st, ws.score.i32.as<int32_t>(), rows, n, d, m->tok_emb, m->dec_pos, ws.x.as<float>());
+  auto store = [&](int layer, const float* qkv) -> int {
+    prof_tag(KC_PREFILL_STORE, 16.0 * rows * d);
+    WB_REQUIRE(launch_prefill_store(st, qkv, nA, n, d, 3 * d, J.S, J.Lmax, J.kc + (size_t)layer * J.kv_layer_stride,
+                                    J.vc + (size_t)layer * J.kv_layer_stride, layer == 0 ? J.tabs : nullptr) == 0,
+               WB_ERR_SHAPE, "prefill: unsupported shape (%d rows x %d positions, S %d, Lmax %d)", nA, n, J.S, J.Lmax);
+    return WB_OK;
+  };
+  WB_TRY(decoder_blocks(m, st, ws, rows, nA, n, ws.segs.as<AttnSeg>(), J.ckv, J.ckv_layer_stride, J.ldkv, store, true));
+  WB_HIP(hipGetLastError());
   return WB_OK;
 }
 

@@ -82,7 +82,24 @@ struct ScoreJob {
   std::vector<float> result_host;
 };
 int run_score(wb_model* m, hipStream_t st, Workspace& ws, ScoreJob& job);
-extern std::mutex g_stateless_mu;       // api.cpp: serialises the stateless entry points (they share the model's scratch)
+
+// Prompt prefill (prefill.hip): one teacher-forced pass over the SAME n prompt tokens for nA active windows (rows packed
+// [a][p]), stopped after the last layer's QKV projection; behind every layer's QKV GEMM the K / V columns go to row p S + a of
+// that layer's paged self-KV cache, and the first layer's launch writes the position tables of parity (n - 1) & 1.
+// Everything is enqueued on `st`, nothing waits; the job's host arrays outlive the enqueued copies.
+struct PrefillJob {
+  int nA = 0, n = 0;
+  std::vector<int32_t> tokens;            // [n]
+  std::vector<int> C, kv_row0;            // per active window: encoder positions, first row of its window in the K/V source
+  const float* ckv = nullptr;             // cached pre-scaled cross K|V: layer i at ckv + i * ckv_layer_stride, rows of ldkv
+  int64_t ckv_layer_stride = 0; int ldkv = 0;
+  int S = 0, Lmax = 0;                    // geometry of the cache: slots per step, positions
+  float* kc = nullptr; float* vc = nullptr; int64_t kv_layer_stride = 0;   // layer i's [Lmax S][d] at kc + i * kv_layer_stride
+  int* tabs = nullptr;                    // [2][S][Lmax]
+  std::vector<AttnSeg> segs_host; std::vector<int32_t> tok_host;
+};
+int run_prefill(wb_model* m, hipStream_t st, Workspace& ws, PrefillJob& job);
+extern std::mutex g_stateless_mu;      // api.cpp: serialises the stateless entry points (they share the model's scratch)
 
 // split-precision fp16 MFMA GEMM when split copies sh / sl ([N][ldwt] fp16) are given and the shape fits, else exact-f32 MFMA
 int gemm_dispatch(const wb_model* m, hipStream_t st, const GemmArgs& a, int ldwt, const uint16_t* sh = nullptr,

@@ -26,6 +26,8 @@ enum KernelClass {
   KC_TS_UPDATE,
   // beam search under the timestamp rules (tsbeam.hip): per-row candidates, per-window bookkeeping
   KC_TSBEAM_ROWS, KC_TSBEAM_UPDATE,
+  // prompt prefill (prefill.hip): one launch per decoder layer of a prefill pass
+  KC_PREFILL_STORE,
   KC_COUNT
 };
 void prof_tag(int cls, double algo_bytes);
@@ -145,6 +147,11 @@ void launch_embed(hipStream_t st, const int32_t* tok, int n_rows, int L, int d, 
                   float* x);
 
 // ---- attention (attention.hip) ---------------------------------------------------
+// Prompt prefill (prefill.hip): K | V columns of qkv [nA n][ld] (row a n + p) -> row p S + a of Kc / Vc [Lmax S][d]; tabs
+// non-null: also tabs[(n - 1) & 1][a][p] = p S + a.  Returns -1 for a shape it does not serve (nothing launched).
+int launch_prefill_store(hipStream_t st, const float* qkv, int nA, int n, int d, int ld, int S, int Lmax, float* Kc, float* Vc,
+                         int* tabs);
+
 struct AttnSeg { int32_t q_row0, q_len, kv_row0, kv_len; };   // one (batch) segment of packed rows
 // O[q][h*64..] = softmax((Q*s)(K*s)^T [+causal]) V per segment and head, head size 64 (mod.rs:493-533)
 // causal: key kv is visible to query q iff kv <= q (positions inside the segment).  kv_len >= 1 for every segment with q_len > 0.

@@ -36,7 +36,8 @@ static const char* const g_kernel_names[KC_COUNT] = {
     "align_dtw (anti-diagonal DTW + backtrace)", "score_logits (LN rows x E^T -> per-split max / sum, target, probes)",
     "score_merge (splits -> lse, log-probs)", "dec_sample_update (Gumbel-max draw + row bookkeeping)",
     "dec_ts_update (timestamp rules + pick + row bookkeeping)",
-    "dec_tsbeam_rows (timestamp rules + B + 1 candidates per row)", "dec_tsbeam_update (beam bookkeeping under the timestamp rules)"};
+    "dec_tsbeam_rows (timestamp rules + B + 1 candidates per row)", "dec_tsbeam_update (beam bookkeeping under the timestamp rules)",
+    "prefill_store (prompt pass K / V -> paged self-KV cache, position tables)"};
 struct PendingLaunch { hipEvent_t a, b; int cls; double bytes; };
 static std::mutex g_prof_mu;
 static std::vector<PendingLaunch> g_pending;

@@ -43,13 +43,9 @@ int session_sample_chain(wb_session* s, const int32_t* prompt, int P, const Samp
   hipStream_t st = s->st;
   const int S = s->S;
   const StepLayout& L = s->lay;
-  {  // prefill: all prompt tokens but the last only feed the KV cache, one row per active window
-    std::vector<int32_t> tok(nA), par(nA);
-    for (int t = 0; t < P - 1; t++) {
-      for (int a = 0; a < nA; a++) { tok[a] = prompt[t]; par[a] = t == 0 ? -1 : a; }
-      WB_TRY(wb_session_step(s, tok.data(), par.data(), wa.data(), nA, 0, 0, nullptr, nullptr));
-    }
-  }
+  // prefill: all prompt tokens but the last only feed the KV cache, one row per active window -- P - 1 steps, or one pass
+  // when the session's prefill mode asks for it (prefill.cpp)
+  WB_TRY(session_prefill_prompt(s, prompt, P, wa.data(), nA));
   const SampleChainLayout sl = make_sample_layout(S, W, std::max(max_depth, 0));
   WB_TRY(s->sc_ctl.ensure((size_t)sl.total_ints * 4));
   WB_TRY(s->sc_topk.ensure((size_t)S * TOPK_MAX * 8));

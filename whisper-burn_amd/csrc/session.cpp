@@ -84,6 +84,7 @@ int session_create(wb_model* m, int n_windows, int max_beams, int padding, wb_se
   s->sample_rate = 16000.0;          // per-use state: a pooled session must not remember its previous caller
   s->smp_best_of = 0; s->smp_depth = 0; s->smp_len.clear(); s->smp_tokens.clear();
   s->has_suppress = false;
+  s->prefill_mode = 0;
   *out = s;
   return WB_OK;
 }

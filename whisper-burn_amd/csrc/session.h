@@ -87,6 +87,8 @@ struct wb_session {
   int prev_n = 0, step = 0;
   bool has_mask = false, decode_ready = false;
   int last_use_mask = 0, last_had_logits = 0;
+  wb::PrefillJob prefill_job;       // host staging of the last prefill pass (session_prefill does not wait for its copies)
+  int prefill_mode = 0;             // wb_session_set_prefill: 0 the chains prefill a prompt step by step, 1 by one pass (prefill.cpp)
   // profiling only: which kernel classes carried the per-row cached K/V bytes of the last enqueued step, and how many
   // chained steps were enqueued since s->step was last advanced (the chained loop advances it once, at its end)
   int prof_cls_cross = -1, prof_cls_self = -1, prof_step_off = 0;
@@ -135,6 +137,13 @@ int session_encode_pcm(wb_session* s, const float* pcm, int64_t n_pcm, const int
 int session_enc_guard_resolve(wb_session* s, bool* reencoded);
 void session_rewind(wb_session* s);      // back to step 0 over the same (re-)encoded window batch
 int session_reserve(wb_session* s, int max_len);
+// Prompt prefill by ONE teacher-forced pass (prefill.cpp): leaves the session where the n steps
+// wb_session_step(tokens[t], parent = t == 0 ? -1 : a, window = wa[a], k = 0), t = 0 .. n - 1, leave it (up to the rounding of
+// exact-f32 MFMA GEMMs against the steps' f32 GEMVs).  Enqueues on s->st and does not wait; the session must be at step 0.
+int session_prefill(wb_session* s, const int32_t* tokens, int n, const int* wa, int nA);
+// the chains' prefill of prompt[0 .. P - 1) for the active windows wa: the pass when the session's mode asks for it (and
+// WHISPER_HIP_PREFILL_PASS allows it) on a fresh session, else P - 1 steps
+int session_prefill_prompt(wb_session* s, const int32_t* prompt, int P, const int* wa, int nA);
 // beam search with the bookkeeping on the device (decode.hip: dec_beam_update_kernel): *handled = false when the shape is not
 // served (the caller runs the host-driven search)
 int session_beam_chain(wb_session* s, const int32_t* prompt, int prompt_len, int beam_size, int eot, int max_depth,

@@ -23,6 +23,7 @@ enum Kind { DEFAULT_ON, OPT_IN, UNSET_OR_1, TRI, INT, STR };
   X(beam_chain, "WHISPER_HIP_BEAM_CHAIN", DEFAULT_ON, "on", "beam bookkeeping on the device; 0: host-driven beam search")            \
   X(persist, "WHISPER_HIP_PERSIST", DEFAULT_ON, "on", "persistent flag-chained greedy kernel; 0: one launch per sublayer")           \
   X(persist_prefill, "WHISPER_HIP_PERSIST_PREFILL", DEFAULT_ON, "on", "the persistent launch runs the prompt itself; 0: host prefill") \
+  X(prefill_pass, "WHISPER_HIP_PREFILL_PASS", DEFAULT_ON, "on", "a session's prefill mode 1 is honoured (one-pass prompt prefill); 0: steps everywhere") \
   X(poll, "WHISPER_HIP_POLL", DEFAULT_ON, "on", "chained greedy: spin on mapped progress flags; 0: copy + synchronise per chunk")    \
   X(speculate, "WHISPER_HIP_SPECULATE", OPT_IN, "off", "chained greedy: enqueue one segment ahead of the finished flags")            \
   X(fuse_sub, "WHISPER_HIP_FUSE_SUB", DEFAULT_ON, "on", "fused self-attention and MLP sublayer kernels; 0: per-matrix GEMVs")        \

@@ -194,9 +194,11 @@ struct Cont { int32_t tok; double score; };
 // `prompt_in` / `P` (optional): the initial sequence of every window instead of the four-token prompt of
 // transcribe.rs:203 -- the retired prompt-conditioning mode (transcribe.rs:188-199) prepends <|startofprev|> and
 // the previous window's last non-special tokens.
+// `sess` (optional): the session behind `step` -- its prompt is prefilled by session_prefill_prompt (steps, or one pass in prefill
+// mode 1) instead of through `step`; the caller holds the session's device turn.
 static int beam_search_windows(const wb_decode_params* p, int W, int V, int S, wb_step_fn step, void* user,
                                int32_t* out_tokens, int32_t row_stride, int32_t* out_lens,
-                               const int32_t* prompt_in = nullptr, int P = 4) {
+                               const int32_t* prompt_in = nullptr, int P = 4, wb_session* sess = nullptr) {
   WB_REQUIRE(p && step && out_tokens && out_lens && W >= 1, WB_ERR_ARG, "beam search: null / bad argument");
   WB_REQUIRE(p->beam_size >= 1 && p->beam_size <= TOPK_MAX, WB_ERR_ARG, "beam_size %d outside [1, %d]", p->beam_size,
              TOPK_MAX);
@@ -213,11 +215,16 @@ static int beam_search_windows(const wb_decode_params* p, int W, int V, int S, w
   const int32_t eot = p->tok_end_of_text;
   auto finished = [&](const Beam& b) { return !b.seq.empty() && b.seq.back() == eot; };   // transcribe.rs:235-241
 
-  // prefill: all prompt tokens but the last only feed the KV cache
+  // prefill: all prompt tokens but the last only feed the KV cache (a session in prefill mode 1: by one pass, prefill.cpp)
   std::vector<int32_t> tok(W), par(W), win(W);
-  for (int t = 0; t < P - 1; t++) {
-    for (int w = 0; w < W; w++) { tok[w] = prompt[t]; par[w] = t == 0 ? -1 : w; win[w] = w; }
-    WB_TRY(step(user, tok.data(), par.data(), win.data(), W, 0, 0, nullptr, nullptr));
+  if (sess) {
+    for (int w = 0; w < W; w++) win[w] = w;
+    WB_TRY(session_prefill_prompt(sess, prompt, P, win.data(), W));
+  } else {
+    for (int t = 0; t < P - 1; t++) {
+      for (int w = 0; w < W; w++) { tok[w] = prompt[t]; par[w] = t == 0 ? -1 : w; win[w] = w; }
+      WB_TRY(step(user, tok.data(), par.data(), win.data(), W, 0, 0, nullptr, nullptr));
+    }
   }
   std::vector<std::vector<Beam>> beams(W);
   std::vector<char> done(W, 0);
@@ -321,7 +328,7 @@ extern "C" int wb_session_decode(wb_session* s, const wb_decode_params* p, int32
                               row_stride, out_lens, &handled));
     if (handled) return WB_OK;
   }
-  return beam_search_windows(p, s->W, s->m->dims.n_vocab, s->S, session_step_thunk, s, out_tokens, row_stride, out_lens);
+  return beam_search_windows(p, s->W, s->m->dims.n_vocab, s->S, session_step_thunk, s, out_tokens, row_stride, out_lens, nullptr, 4, s);
 }
 
 extern "C" int wb_session_decode_prompt(wb_session* s, const wb_decode_params* p, const int32_t* prompt,
@@ -330,9 +337,12 @@ extern "C" int wb_session_decode_prompt(wb_session* s, const wb_decode_params* p
   WB_REQUIRE(prompt_len >= 1, WB_ERR_ARG, "wb_session_decode_prompt: empty prompt");
   WB_REQUIRE(p->beam_size >= 1 && p->beam_size <= s->max_beams, WB_ERR_ARG, "beam_size %d outside [1, %d]",
              p->beam_size, s->max_beams);
+  // (the turn from here to the last synchronisation: a one-pass prefill enqueues its launches without waiting, so they must
+  // not run outside it; the steps take it again, recursively)
+  wb::GpuTurn turn(s->device);
   if (!s->decode_ready || s->Lmax < prompt_len + p->max_depth) WB_TRY(session_reserve(s, prompt_len + p->max_depth + 1));
   return beam_search_windows(p, s->W, s->m->dims.n_vocab, s->S, session_step_thunk, s, out_tokens, row_stride, out_lens,
-                             prompt, prompt_len);
+                             prompt, prompt_len, s);
 }
 
 // transcribe.rs:23-74 with the prompt conditioning of :43-50 / :188-199 switched back on (the reference shadows it

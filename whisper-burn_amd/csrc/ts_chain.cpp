@@ -68,13 +68,9 @@ int session_ts_chain(wb_session* s, const wb_timestamp_params& tp, const int32_t
   hipStream_t st = s->st;
   const int S = s->S;
   const StepLayout& L = s->lay;
-  {  // prefill: all prompt tokens but the last only feed the KV cache, one row per active window
-    std::vector<int32_t> tok(nA), par(nA);
-    for (int t = 0; t < P - 1; t++) {
-      for (int a = 0; a < nA; a++) { tok[a] = prompt[t]; par[a] = t == 0 ? -1 : a; }
-      WB_TRY(wb_session_step(s, tok.data(), par.data(), wa.data(), nA, 0, 0, nullptr, nullptr));
-    }
-  }
+  // prefill: all prompt tokens but the last only feed the KV cache, one row per active window -- P - 1 steps, or one pass
+  // when the session's prefill mode asks for it (prefill.cpp)
+  WB_TRY(session_prefill_prompt(s, prompt, P, wa.data(), nA));
   const TsChainLayout tl = make_ts_layout(S, W, std::max(max_depth, 0));
   WB_TRY(s->ts_ctl.ensure((size_t)tl.total_ints * 4));
   WB_TRY(s->ts_topk.ensure((size_t)S * TOPK_MAX * 8));
@@ -363,13 +359,21 @@ int wb_segments_from_tokens(const int32_t* tokens, int32_t n, int32_t tok_timest
   return WB_OK;
 }
 
-// The seek loop of wb_waveform_to_segments; bp non-null: every window by beam search (wb_waveform_to_segments_beam).
+// What wb_waveform_to_segments_conditioned adds to the seek loop (the rule is stated once, in whisper_hip.h)
+struct SeekCond {
+  int32_t sot_prev, on, max_prompt;
+  const int32_t* initial; int32_t n_initial;
+  int64_t* win_seek; int32_t* win_prompt_len; int32_t win_cap;
+};
+
+// The seek loop of wb_waveform_to_segments; bp non-null: every window by beam search (wb_waveform_to_segments_beam); cond
+// non-null: every window's prompt carries the history (wb_waveform_to_segments_conditioned).
 static int waveform_segments_loop(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
                                   const wb_timestamp_params* tp, const wb_beam_params* bp, const uint8_t* suppress,
                                   const uint8_t* suppress_first, const int32_t* prompt, int32_t prompt_len, float* seg_start,
                                   float* seg_end_time, int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap,
                                   int32_t* n_segments, int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens,
-                                  int32_t* n_windows) {
+                                  int32_t* n_windows, const SeekCond* cond = nullptr) {
   WB_REQUIRE(m && pcm && p && tp && suppress && prompt && seg_start && seg_end_time && seg_tok_begin && seg_tok_end && n_segments &&
                  text_tokens && n_text_tokens, WB_ERR_ARG, "wb_waveform_to_segments: null argument");
   WB_REQUIRE(sample_rate > 0 && tp->seconds_per_timestamp > 0.f && prompt_len >= 1 && p->max_depth >= 0, WB_ERR_ARG,
@@ -384,10 +388,25 @@ static int waveform_segments_loop(wb_model* m, const float* pcm, int64_t n, int 
   if (bp) WB_TRY(check_beam_params(*tp, *bp, MAX_BEAMS, &max_cand));
   for (int i = 0; i < prompt_len; i++)
     WB_REQUIRE(prompt[i] >= 0 && prompt[i] < m->dims.n_vocab, WB_ERR_ARG, "prompt token %d out of range", prompt[i]);
+  std::vector<int32_t> history, wprompt;
+  int hist_cap = 0;
+  if (cond) {
+    const int V = m->dims.n_vocab;
+    WB_REQUIRE(cond->n_initial >= 0 && (cond->n_initial == 0 || cond->initial) && cond->win_cap >= 0, WB_ERR_ARG,
+               "wb_waveform_to_segments_conditioned: bad argument");
+    WB_REQUIRE(cond->sot_prev >= 0 && cond->sot_prev < V, WB_ERR_ARG, "start-of-prev token %d out of range [0,%d)", cond->sot_prev, V);
+    for (int i = 0; i < cond->n_initial; i++)
+      WB_REQUIRE(cond->initial[i] >= 0 && cond->initial[i] < V, WB_ERR_ARG, "initial prompt token %d out of range [0,%d)",
+                 cond->initial[i], V);
+    history.assign(cond->initial, cond->initial + cond->n_initial);
+    hist_cap = cond->max_prompt < 0 ? std::max(0, m->dims.n_text_ctx / 2 - 1) : cond->max_prompt;
+  }
   const int64_t wlen = wb_max_waveform_samples(m->max_mel_frames() - p->padding);
   const double samples_per_ts = (double)tp->seconds_per_timestamp * (double)sample_rate;
   const int tb = tp->tok_timestamp_begin, nts = tp->n_timestamps;
-  const int stride = prompt_len + p->max_depth;
+  const int base_prompt_len = prompt_len;
+  const int32_t* base_prompt = prompt;
+  const int stride = (hist_cap > 0 ? 1 + hist_cap : 0) + prompt_len + p->max_depth;
   std::vector<int32_t> row((size_t)stride), sb((size_t)p->max_depth + 1), se((size_t)p->max_depth + 1);
   std::vector<float> t0((size_t)p->max_depth + 1), t1((size_t)p->max_depth + 1);
   int ns = 0, nw = 0;
@@ -397,6 +416,20 @@ static int waveform_segments_loop(wb_model* m, const float* pcm, int64_t n, int 
     const int win_index = (int)((double)len / samples_per_ts);       // whole timestamp units inside the window
     wb_timestamp_params wtp = *tp;
     if (wtp.max_timestamp_index < 0 || wtp.max_timestamp_index > win_index) wtp.max_timestamp_index = win_index;
+    // the window's prompt: [start-of-prev] + the last hist_cap tokens of the history + prompt; no history section: prompt alone
+    const int n_hist = (int)std::min<size_t>(history.size(), (size_t)hist_cap);
+    if (n_hist > 0) {
+      wprompt.assign(1, cond->sot_prev);
+      wprompt.insert(wprompt.end(), history.end() - n_hist, history.end());
+      wprompt.insert(wprompt.end(), base_prompt, base_prompt + base_prompt_len);
+      prompt = wprompt.data(); prompt_len = (int32_t)wprompt.size();
+    } else {
+      prompt = base_prompt; prompt_len = base_prompt_len;
+    }
+    if (cond && nw < cond->win_cap) {
+      if (cond->win_seek) cond->win_seek[nw] = seek;
+      if (cond->win_prompt_len) cond->win_prompt_len[nw] = prompt_len;
+    }
     wb_session* s = nullptr;
     int rc = session_create(m, 1, bp ? bp->beam_size : std::max(1, tp->best_of), p->padding, &s);
     int32_t rlen = 0;
@@ -404,6 +437,7 @@ static int waveform_segments_loop(wb_model* m, const float* pcm, int64_t n, int 
       s->sample_rate = (double)sample_rate;
       rc = session_encode_pcm(s, pcm, n, &seek, &len, false);
       if (rc == WB_OK) rc = wb_session_set_suppress(s, suppress, suppress_first);
+      if (rc == WB_OK && n_hist > 0) rc = wb_session_set_prefill(s, 1);     // a history section: the prompt is prefilled by one pass
       if (rc == WB_OK)
         rc = bp ? wb_session_decode_timestamps_beam(s, p, &wtp, bp, prompt, prompt_len, nullptr, row.data(), stride, &rlen, nullptr, nullptr)
                 : wb_session_decode_timestamps(s, p, &wtp, prompt, prompt_len, nullptr, nullptr, row.data(), stride, &rlen, nullptr,
@@ -428,6 +462,12 @@ static int waveform_segments_loop(wb_model* m, const float* pcm, int64_t n, int 
         }
       seg_tok_end[ns] = (int32_t)nt;
       ns++;
+    }
+    if (cond) {
+      // the tokens the window's segments cover (timestamps included, end-of-text and the tail behind the last pair not), then
+      // Whisper's two reset rules
+      if (k > 0) history.insert(history.end(), gen + sb[0], gen + se[k - 1]);
+      if (!cond->on || tp->temperature > 0.5f) history.clear();
     }
     int64_t step = (int64_t)std::llround((double)adv * samples_per_ts);
     if (step <= 0) step = len;                     // progress: an advance of 0 moves a whole window
@@ -458,6 +498,21 @@ int wb_waveform_to_segments_beam(wb_model* m, const float* pcm, int64_t n, int s
   return waveform_segments_loop(m, pcm, n, sample_rate, p, tp, bp, suppress, suppress_first, prompt, prompt_len, seg_start,
                                 seg_end_time, seg_tok_begin, seg_tok_end, seg_cap, n_segments, text_tokens, text_cap, n_text_tokens,
                                 n_windows);
+}
+
+int wb_waveform_to_segments_conditioned(wb_model* m, const float* pcm, int64_t n, int sample_rate, const wb_decode_params* p,
+                                        const wb_timestamp_params* tp, const wb_beam_params* bp, const uint8_t* suppress,
+                                        const uint8_t* suppress_first, const int32_t* prompt, int32_t prompt_len,
+                                        int32_t tok_start_of_prev, int32_t condition_on_previous_text, int32_t max_prompt_tokens,
+                                        const int32_t* initial_prompt, int32_t n_initial_prompt, float* seg_start,
+                                        float* seg_end_time, int32_t* seg_tok_begin, int32_t* seg_tok_end, int32_t seg_cap,
+                                        int32_t* n_segments, int32_t* text_tokens, int64_t text_cap, int64_t* n_text_tokens,
+                                        int32_t* n_windows, int64_t* win_seek, int32_t* win_prompt_len, int32_t win_cap) {
+  const SeekCond cond{tok_start_of_prev, condition_on_previous_text, max_prompt_tokens, initial_prompt, n_initial_prompt,
+                      win_seek, win_prompt_len, win_cap};
+  return waveform_segments_loop(m, pcm, n, sample_rate, p, tp, bp, suppress, suppress_first, prompt, prompt_len, seg_start,
+                                seg_end_time, seg_tok_begin, seg_tok_end, seg_cap, n_segments, text_tokens, text_cap, n_text_tokens,
+                                n_windows, &cond);
 }
 
 }  // extern "C"

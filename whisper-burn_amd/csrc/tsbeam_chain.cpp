@@ -177,13 +177,9 @@ int session_tsbeam_chain(wb_session* s, const wb_timestamp_params& tp, const wb_
   hipStream_t st = s->st;
   const int S = s->S;
   const StepLayout& L = s->lay;
-  {  // prefill: all prompt tokens but the last only feed the KV cache, one row per active window
-    std::vector<int32_t> tok(nA), par(nA);
-    for (int t = 0; t < P - 1; t++) {
-      for (int a = 0; a < nA; a++) { tok[a] = prompt[t]; par[a] = t == 0 ? -1 : a; }
-      WB_TRY(wb_session_step(s, tok.data(), par.data(), wa.data(), nA, 0, 0, nullptr, nullptr));
-    }
-  }
+  // prefill: all prompt tokens but the last only feed the KV cache, one row per active window -- P - 1 steps, or one pass
+  // when the session's prefill mode asks for it (prefill.cpp)
+  WB_TRY(session_prefill_prompt(s, prompt, P, wa.data(), nA));
   const bool start_finished = prompt[P - 1] == eot;       // nothing is generated behind an end-of-text
   const TsBeamLayout bl = make_tsbeam_layout(S, W, (start_finished || max_depth < 0) ? 0 : max_depth);
   WB_TRY(s->tb_ctl.ensure((size_t)bl.total_ints * 4));

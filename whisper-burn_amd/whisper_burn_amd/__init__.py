@@ -7,7 +7,7 @@ from .model import (WB_BF16, WB_F32, Session, Whisper, burn_record_tensors, deco
                     window_extents, dtw_start_positions, waveform_to_token_times, waveform_to_token_scores,
                     detect_language, logprob_gather, sample_rows, SampleParams, TimestampParams, timestamp_rows,
                     segments_from_tokens, waveform_to_segments, BeamParams, timestamp_beam_rows, timestamp_beam_search_device,
-                    FallbackParams, fallback_decide,
+                    FallbackParams, fallback_decide, prefill_store,
                     compression_ratio, ratio_from_tokenizer, waveform_to_tokens_fallback)
 from .tokens import SpecialTokens  # noqa: F401
 from ._lib import WbError  # noqa: F401

@@ -221,6 +221,16 @@ SIGNATURES = {
                                                C.POINTER(WbTimestampParams), C.POINTER(WbBeamParams), c_uint8_p, c_uint8_p,
                                                c_int32_p, C.c_int32, c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int32,
                                                c_int32_p, c_int32_p, C.c_int64, c_int64_p, c_int32_p]),
+    "wb_session_set_prefill": (C.c_int, [C.c_void_p, C.c_int]),
+    "wb_session_prefill": (C.c_int, [C.c_void_p, c_int32_p, C.c_int32, c_uint8_p]),
+    "wb_prefill_store": (C.c_int, [C.c_int, c_float_p] + [C.c_int32] * 6 + [c_float_p, c_float_p, c_int32_p]),
+    "wb_session_self_kv": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p]),
+    "wb_waveform_to_segments_conditioned": (C.c_int, [C.c_void_p, c_float_p, C.c_int64, C.c_int, C.POINTER(WbDecodeParams),
+                                                      C.POINTER(WbTimestampParams), C.POINTER(WbBeamParams), c_uint8_p,
+                                                      c_uint8_p, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                      c_int32_p, C.c_int32, c_float_p, c_float_p, c_int32_p, c_int32_p,
+                                                      C.c_int32, c_int32_p, c_int32_p, C.c_int64, c_int64_p, c_int32_p,
+                                                      c_int64_p, c_int32_p, C.c_int32]),
     "wb_first_repetition_end": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_repetition_period": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_find_repeated_tokens_index": (C.c_int, [c_int32_p, C.c_int64, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),

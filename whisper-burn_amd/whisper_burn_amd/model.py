@@ -269,6 +269,16 @@ def timestamp_rows(logits, tp: WbTimestampParams, n_gen, prev1, prev2, last_ts, 
     return tok, lp, forced, stats, int(err[0])
 
 
+def prefill_store(qkv, nA: int, n: int, d: int, S: int, Lmax: int, Kc, Vc, tabs, device: int = 0):
+    """The store kernel of the one-pass prompt prefill alone (wb_prefill_store, a test hook): qkv [nA * n, ld]; Kc / Vc
+    [Lmax * S, d] f32 and tabs [2, S, Lmax] i32 are updated in place."""
+    q = _f32(qkv)
+    assert q.ndim == 2 and q.shape[0] == nA * n
+    for a, shape, dt in ((Kc, (Lmax * S, d), np.float32), (Vc, (Lmax * S, d), np.float32), (tabs, (2, S, Lmax), np.int32)):
+        assert a.dtype == dt and a.flags.c_contiguous and a.shape == shape, (a.dtype, a.shape, shape)
+    check(_lib.load().wb_prefill_store(device, _fp(q), nA, n, d, q.shape[1], S, Lmax, _fp(Kc), _fp(Vc), _ip(tabs)))
+
+
 def segments_from_tokens(tokens, tp: WbTimestampParams, eot: int, window_index: int):
     """Whisper transcribe()'s slicing of one window's generated tokens (wb_segments_from_tokens, host only): a list of
     dict(begin, end, start, end_time) -- token index range and seconds relative to the window -- and the advance index."""
@@ -285,11 +295,15 @@ def segments_from_tokens(tokens, tp: WbTimestampParams, eot: int, window_index: 
 
 def waveform_to_segments(whisper: "Whisper", st: SpecialTokens, waveform, sample_rate: int = 16000, params=None,
                          timestamps: Optional[WbTimestampParams] = None, suppress=None, suppress_first=None, prompt=None,
-                         beam: Optional[WbBeamParams] = None):
+                         beam: Optional[WbBeamParams] = None, condition_on_previous_text: bool = False, initial_prompt=None,
+                         max_prompt_tokens: int = -1, return_windows: bool = False):
     """Long-form transcription by timestamps (wb_waveform_to_segments): the window moves by the last decoded timestamp.
     Returns (segments, tokens, n_windows): segments = dict(start, end, tokens) with absolute seconds and the segment's
     non-timestamp tokens; tokens = their concatenation.  beam: BeamParams -- every window by beam search under the rules
-    (wb_waveform_to_segments_beam); None: greedy / best-of-n as `timestamps` says."""
+    (wb_waveform_to_segments_beam); None: greedy / best-of-n as `timestamps` says.
+    condition_on_previous_text / initial_prompt (token ids) / max_prompt_tokens (-1: n_text_ctx / 2 - 1): every window's prompt
+    carries [<|startofprev|>] + the tail of the text before it (wb_waveform_to_segments_conditioned states the rule); such
+    prompts are prefilled by one pass.  return_windows: a fourth result dict(seek, prompt_len), one entry per window."""
     from .tokens import default_suppress
     wav = _f32(waveform).reshape(-1)
     p = params if params is not None else decode_params(st)
@@ -312,6 +326,21 @@ def waveform_to_segments(whisper: "Whisper", st: SpecialTokens, waveform, sample
     ns, nw, nt = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     tail = (_u8p(sup), _u8p(sup1), _ip(pr), len(pr), _fp(t0), _fp(t1), _ip(b), _ip(e), seg_cap, C.byref(ns), _ip(text), text_cap,
             C.byref(nt), C.byref(nw))
+    init = _i32([] if initial_prompt is None else list(initial_prompt))
+    if condition_on_previous_text or len(init) or return_windows:
+        win_seek, win_plen = np.zeros(n_win_max, dtype=np.int64), np.zeros(n_win_max, dtype=np.int32)
+        # (return_windows alone: no history can form, <|startofprev|> is never used -- a tokenizer without one still gets its windows)
+        sop = int(st.start_of_prev) if (condition_on_previous_text or len(init)) else max(int(st.start_of_prev), 0)
+        check(_lib.load().wb_waveform_to_segments_conditioned(
+            whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p), C.byref(tp), C.byref(beam) if beam is not None else None,
+            *tail[:4], sop, int(bool(condition_on_previous_text)), int(max_prompt_tokens),
+            _ip(init) if len(init) else None, len(init), *tail[4:], win_seek.ctypes.data_as(_lib.c_int64_p), _ip(win_plen),
+            n_win_max))
+        toks = text[:nt.value].tolist()
+        segs = [dict(start=float(t0[i]), end=float(t1[i]), tokens=toks[b[i]:e[i]]) for i in range(ns.value)]
+        if not return_windows:
+            return segs, toks, int(nw.value)
+        return segs, toks, int(nw.value), dict(seek=win_seek[:nw.value].tolist(), prompt_len=win_plen[:nw.value].tolist())
     if beam is None:
         check(_lib.load().wb_waveform_to_segments(whisper._h, _fp(wav), len(wav), sample_rate, C.byref(p), C.byref(tp), *tail))
     else:
@@ -991,6 +1020,34 @@ class Session:
         lens = np.zeros(self.n_windows, dtype=np.int32)
         check(_lib.load().wb_session_decode(self._h, C.byref(params), _ip(toks), stride, _ip(lens)))
         return [toks[i, :lens[i]].tolist() for i in range(self.n_windows)]
+
+    def decode_prompt(self, params: WbDecodeParams, prompt) -> List[List[int]]:
+        """Session.decode behind a caller's prompt (wb_session_decode_prompt): the host-driven beam search of params.beam_size."""
+        pr = _i32(list(prompt))
+        stride = len(pr) + params.max_depth + 4
+        toks = np.zeros((self.n_windows, stride), dtype=np.int32)
+        lens = np.zeros(self.n_windows, dtype=np.int32)
+        check(_lib.load().wb_session_decode_prompt(self._h, C.byref(params), _ip(pr), len(pr), _ip(toks), stride, _ip(lens)))
+        return [toks[i, :lens[i]].tolist() for i in range(self.n_windows)]
+
+    def set_prefill(self, mode: int) -> None:
+        """How the decode calls feed a prompt to the self-KV cache (wb_session_set_prefill): 0 one step per token (default),
+        1 one teacher-forced pass over all prompt positions."""
+        check(_lib.load().wb_session_set_prefill(self._h, int(mode)))
+
+    def prefill(self, tokens, active=None) -> None:
+        """The one-pass prompt prefill alone (wb_session_prefill), on a fresh or rewound session: the same `tokens` for every
+        active window (active [W] of 0 / 1, default all); step() continues behind it with parent = index among the active."""
+        t = _i32(list(tokens))
+        act = np.ascontiguousarray(active, dtype=np.uint8) if active is not None else None
+        check(_lib.load().wb_session_prefill(self._h, _ip(t) if len(t) else None, len(t), _u8p(act)))
+
+    def self_kv(self, layer: int, slot: int, n_pos: int):
+        """Cached self-attention K (pre-scaled) and V of a live slot, [n_pos, d] each (wb_session_self_kv, a test hook)."""
+        d = self._w.dims["n_text_state"]
+        K, V = np.full((n_pos, d), np.nan, dtype=np.float32), np.full((n_pos, d), np.nan, dtype=np.float32)
+        check(_lib.load().wb_session_self_kv(self._h, int(layer), int(slot), int(n_pos), _fp(K), _fp(V)))
+        return K, V
 
     def rewind(self) -> None:
         """Back to step 0 over the same encoded windows (wb_session_rewind): another decode costs decode steps only."""

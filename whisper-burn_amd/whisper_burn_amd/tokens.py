@@ -117,6 +117,10 @@ class TokenizerAdapter:
     def decode(self, tokens, skip_special: bool = True) -> str:             # token.rs:32-35
         return self.tok.decode([int(t) for t in tokens], skip_special_tokens=skip_special)
 
+    def encode(self, text: str) -> list:
+        """The ids of `text`, without added special tokens (Whisper's tokenizer.encode: what an initial prompt goes through)."""
+        return [int(t) for t in self.tok.encode(text, add_special_tokens=False).ids]
+
     def is_special(self, token: int) -> bool:                               # token.rs:37-43
         try:
             return self.tok.decode([int(token)], skip_special_tokens=True) == ""

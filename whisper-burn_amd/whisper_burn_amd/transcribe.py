@@ -34,6 +34,9 @@ times in seconds; the transcript is then the segments' text.  Not together with 
 With it, `--beam-size N` (1 .. 7) decodes every window by beam search under the timestamp rules
 (wb_waveform_to_segments_beam: Whisper's BeamSearchDecoder on the device), optionally with `--patience X` (>= 1, default 1)
 and `--length-penalty A` (default: rank by average log-prob); the three flags are rejected without `--segments`.
+`--condition-on-previous-text` prompts every window with the text decoded before it (behind <|startofprev|>, Whisper's
+condition_on_previous_text) and `--initial-prompt TEXT` starts that history with TEXT, encoded by the tokenizer
+(wb_waveform_to_segments_conditioned; such prompts are prefilled by one pass); both are rejected without `--segments`.
 
 One addition: with `WHISPER_HIP_RESAMPLE=1` in the environment a mono WAV of another sample rate (the bundled
 22 050 Hz audio.wav, which the reference sends through `sox`, README.md:69-74) is resampled to 16 kHz on the GPU
@@ -59,7 +62,7 @@ def main(argv=None) -> int:
     segments_file = None
     extra = argv[5:]
     usage = (f"Usage: {argv[0]} <model name> <audio file> <lang> <transcription file> [--frontend fft|reference] "
-             f"[--token-times PATH] [--scores PATH] [--segments PATH [--beam-size N [--patience X] [--length-penalty A]]] [--fallback [--temperatures T0,T1,..] [--best-of N] [--seed N] "
+             f"[--token-times PATH] [--scores PATH] [--segments PATH [--beam-size N [--patience X] [--length-penalty A]] [--condition-on-previous-text] [--initial-prompt TEXT]] [--fallback [--temperatures T0,T1,..] [--best-of N] [--seed N] "
              f"[--logprob-threshold X] [--no-speech-threshold X] [--compression-ratio-threshold X]]")
     fallback = False
     fb = {}                                     # keyword arguments of FallbackParams given on the command line
@@ -69,8 +72,19 @@ def main(argv=None) -> int:
                "--compression-ratio-threshold": ("compression_ratio_threshold", float)}
     beam = {}                                   # keyword arguments of BeamParams given on the command line
     beam_opts = {"--beam-size": ("beam_size", int), "--patience": ("patience", float), "--length-penalty": ("length_penalty", float)}
+    condition = False
+    initial_prompt = None
     while extra:                                # (other trailing arguments are ignored, as before)
-        if extra[0] in beam_opts:
+        if extra[0] == "--condition-on-previous-text":
+            condition = True
+            extra = extra[1:]
+        elif extra[0] == "--initial-prompt":
+            if len(extra) < 2:
+                print(usage, file=sys.stderr)
+                return 1
+            initial_prompt = extra[1]
+            extra = extra[2:]
+        elif extra[0] in beam_opts:
             key, conv = beam_opts[extra[0]]
             try:
                 beam[key] = conv(extra[1])
@@ -110,6 +124,10 @@ def main(argv=None) -> int:
     if beam and (segments_file is None or "beam_size" not in beam):
         print("--beam-size / --patience / --length-penalty (beam search under the timestamp rules) need --segments and --beam-size\n"
               + usage, file=sys.stderr)
+        return 1
+    if (condition or initial_prompt is not None) and segments_file is None:
+        print("--condition-on-previous-text / --initial-prompt (prompts conditioned on previous text) need --segments\n" + usage,
+              file=sys.stderr)
         return 1
     if fallback and times_file is not None:
         print("--token-times is not available together with --fallback\n" + usage, file=sys.stderr)
@@ -190,8 +208,14 @@ def main(argv=None) -> int:
             if st.n_timestamps == 0:
                 raise ValueError("the tokenizer has no timestamp tokens (<|0.00|> ...)")
             sup, sup_first = default_suppress(st, bpe)
+            init = None
+            if initial_prompt is not None and initial_prompt.strip():       # Whisper: tokenizer.encode(" " + initial_prompt.strip())
+                init = bpe.encode(" " + initial_prompt.strip())
+            if (condition or init) and st.start_of_prev < 0:
+                raise ValueError("the tokenizer has no <|startofprev|> token")
             segments, _tokens, _ = wb.waveform_to_segments(whisper, st, waveform, sample_rate, suppress=sup, suppress_first=sup_first,
-                                                           beam=wb.BeamParams(**beam) if beam else None)
+                                                           beam=wb.BeamParams(**beam) if beam else None,
+                                                           condition_on_previous_text=condition, initial_prompt=init)
             text = bpe.decode(_tokens, True)
         elif fallback:
             st = bpe.special_tokens(lang)
