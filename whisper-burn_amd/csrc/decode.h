@@ -478,5 +478,7 @@ bool dec_fused_supported(int d);
 int dec_mlp_fused_planes(int d);
 void launch_dec_mlp_fused(hipStream_t st, const MlpFusedArgs& a, int n_rows_hint);
 void launch_dec_attn_fused(hipStream_t st, const AttnFusedArgs& a, int n_rows_hint);
+// test-only: the d = 384 self-attention sublayer with n_reg (2 or 4) QKV weight rounds in registers; -1: not served
+int launch_dec_attn_fused_rounds(hipStream_t st, const AttnFusedArgs& a, int n_rows_hint, int n_reg);
 
 }  // namespace wb

@@ -46,6 +46,13 @@ __global__ __launch_bounds__(512) void dec_attn_fused_kernel(AttnFusedArgs a) {
   __shared__ AttnLds<DPL> sm;
   dec_attn_body<DPL, false>(a, blockIdx.x, blockIdx.y, PsStep(), sm);
 }
+// test-only (launch_dec_attn_fused_rounds): the d = 384 body with FOUR register rounds, so that the four-round sequence of the
+// persistent kernel's role (streamed form) runs next to the two-round one, dec_attn_fused_kernel<6>, on the same inputs.  (Not a
+// template over the count: a second kernel around the two-round body changes how the product kernel's lambdas are inlined.)
+__global__ __launch_bounds__(512) void dec_attn_fused_rounds4_kernel(AttnFusedArgs a) {
+  __shared__ AttnLds<6> sm;
+  dec_attn_body<6, false, 0, 4>(a, blockIdx.x, blockIdx.y, PsStep(), sm);
+}
 template <int DPL, int NP>
 __global__ __launch_bounds__(512) void dec_cross_fused_kernel(CrossFusedArgs a) {
   __shared__ CrossLds<DPL, NP> sm;
@@ -237,6 +244,14 @@ void launch_dec_attn_fused(hipStream_t st, const AttnFusedArgs& a, int n_rows_hi
   if (a.d == 128) WB_KLAUNCH((dec_attn_fused_kernel<2>), grid, block, 0, st, a);
   else if (a.d == 384) WB_KLAUNCH((dec_attn_fused_kernel<6>), grid, block, 0, st, a);
   else WB_KLAUNCH((dec_attn_fused_kernel<8>), grid, block, 0, st, a);
+}
+
+int launch_dec_attn_fused_rounds(hipStream_t st, const AttnFusedArgs& a, int n_rows_hint, int n_reg) {
+  if (a.d != 384 || (n_reg != 2 && n_reg != 4)) return -1;
+  const dim3 grid(8, n_rows_hint), block(512);
+  if (n_reg == 2) WB_KLAUNCH((dec_attn_fused_kernel<6>), grid, block, 0, st, a);
+  else WB_KLAUNCH(dec_attn_fused_rounds4_kernel, grid, block, 0, st, a);
+  return 0;
 }
 
 }  // namespace wb

@@ -687,7 +687,18 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
 // out-projection slice.  The attention phases and the out-projection do not wait on memory.
 // res (persistent mode): the block's resident operands (ResGeom: RS float4 slots per thread, filled by dec_attn_res_fill at
 // kernel entry), null = everything is streamed.
-template <int DPL, bool PS, int RS = 0>
+// NREG: QKV weight rounds requested into registers before the first wait (2 or 4).  4 is for d = 384 (NIT = 6), where with the
+// two LDS rounds of the resident region no weight load is left behind the persistent kernel's wait: registers 0, 1, 4, 5, LDS
+// 2, 3.  Without the region the four sets hold rounds 0 - 3 and rounds 4, 5 follow into the first two as those are consumed.
+// The accumulation order is 0, 1, 2, ... with the same operands for every NREG and either path: the bits do not depend on it.
+#ifndef WB_ATTN_NREG_PS6
+#define WB_ATTN_NREG_PS6 4                          // (-DWB_ATTN_NREG_PS6=2: the two-round variant, for A/B builds with tools/build_exp.sh)
+#endif
+// (the persistent instances without a resident region, RS = 0, sit hardest at the register limit: with four rounds their
+// scratch grew from 132 / 16 B to about 400 B per lane, so they keep two)
+template <int DPL, bool PS, int RS>
+constexpr int attn_nreg() { return (PS && DPL == 6 && RS > 0) ? (WB_ATTN_NREG_PS6) : 2; }
+template <int DPL, bool PS, int RS = 0, int NREG = attn_nreg<DPL, PS, RS>()>
 __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int h, const int r, const PsStep& ps, AttnLds<DPL>& sm,
                                               const float4* res = nullptr) {
   constexpr int NT = 512;
@@ -721,8 +732,9 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   const int seg = lane >> 4, c4 = (lane & 15) * 4;
   const bool seg_ok = seg < 3;
   const float* wq = a.Wqkv + (int64_t)(wave * KW) * a.ldqkv + (seg_ok ? seg : 0) * d + h * 64 + c4;
-  float4 wr[2][RK];
-  auto load_round = [&](float4 (&w)[RK], int it) {
+  static_assert(NREG == 2 || (NREG == 4 && NIT == 6 && (RG::NRND == 0 || RG::NRND == 2)), "register rounds: 2, or 4 of the 6 at d = 384");
+  float4 wr[NREG][RK];
+  auto load_round =[&](float4 (&w)[RK], int it) {
 #pragma unroll
     for (int j = 0; j < RK; j++) w[j] = ld_w4(wq + (int64_t)(RK * it + j) * a.ldqkv);
   };
@@ -766,7 +778,12 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
       g_own = gld(a.ln_g + own_col); b_own = gld(a.ln_b + own_col);
       load_round(wr[0], 0);
       if (NIT > 1) load_round(wr[1], 1);
-      if constexpr (PS) { if (tid < 192) qbias = gld(a.bqkv + (tid >> 6) * d + h * 64 + (tid & 63)); }
+      if constexpr (NREG == 4) {                    // (resident: rounds 2, 3 are in LDS -> the last two; else the next two)
+        const int it2 = (RG::NRND > 0 && res != nullptr) ? 2 + RG::NRND : 2;
+        load_round(wr[2], it2);
+        load_round(wr[3], it2 + 1);
+      }
+      if constexpr (PS && NREG == 2) { if (tid < 192) qbias = gld(a.bqkv + (tid >> 6) * d + h * 64 + (tid & 63)); }
     };
     if constexpr (PS) {
       // persistent mode: the first weight rounds are in flight (or landed) while the block waits; the wait is a PRE-wake
@@ -775,7 +792,7 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
 #if !defined(WB_PS_DRY)
       if (!ps.known_dead) {
         load_weights();
-        load_cache_tile();
+        if constexpr (NREG == 2) load_cache_tile();  // (four rounds: behind the sweep, below -- the granules need the registers)
       }
 #endif
       if (!ps_wait(ps)) return false;
@@ -817,6 +834,14 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
       }
       xfold = v;
       if (tid < d) hs[tid] = v;
+#if !defined(WB_PS_DRY)
+      // four register rounds: the cached K / V tile is requested here, with the sweep's granule registers free again.  Nothing
+      // else is in flight, and the scores that consume it lie behind LayerNorm, the QKV rounds and three barriers.
+      if constexpr (NREG == 4) {
+        load_cache_tile();
+        if (tid < 192) qbias = gld(a.bqkv + (tid >> 6) * d + h * 64 + (tid & 63));
+      }
+#endif
     } else {
     float v = a.x_in[(int64_t)r * d + c];
     constexpr int FP = 32;                          // planes per round: 4 d / 64 <= 32 MLP planes in ONE round trip
@@ -874,6 +899,40 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
   const int nres = (RG::NRND > 0 && res != nullptr) ? RG::NRND : 0;
   const int nreg = NIT - nres;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (NREG == 4) {
+    // Four register sets, written out (a run-time index into wr[] would send it to scratch).  Resident: 0, 1 from registers,
+    // 2, 3 from LDS, 4, 5 from registers -- nothing is requested behind the wait.  Streamed: rounds 4, 5 follow into the first
+    // two sets as those are consumed, in flight under rounds 2 and 3.
+    auto fma_round = [&](const float4 (&w)[RK], const int kb) {
+#pragma unroll
+      for (int j = 0; j < RK; j++) {
+        const float xv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xn_own), kb + j));
+        acc[0] += xv * w[j].x; acc[1] += xv * w[j].y; acc[2] += xv * w[j].z; acc[3] += xv * w[j].w;
+      }
+    };
+    fma_round(wr[0], 0);
+    if (nres == 0) load_round(wr[0], 4);
+    fma_round(wr[1], RK);
+    if (nres == 0) load_round(wr[1], 5);
+    if (nres > 0) {
+      if constexpr (RG::NRND > 0) {
+#pragma unroll 1
+        for (int q = 0; q < RG::NRND; q++) {
+          float4 wl[RK];
+#pragma unroll
+          for (int j = 0; j < RK; j++) wl[j] = res_ld(res, 0, RG::QL, q * RK + j, RG::q_holder(wave, lane));
+          fma_round(wl, RK * (2 + q));
+        }
+      }
+      fma_round(wr[2], 4 * RK);
+      fma_round(wr[3], 5 * RK);
+    } else {
+      fma_round(wr[2], 2 * RK);
+      fma_round(wr[3], 3 * RK);
+      fma_round(wr[0], 4 * RK);
+      fma_round(wr[1], 5 * RK);
+    }
+  } else {
 #pragma unroll 1
   for (int n = 0; n < nreg; n += 2) {
 #pragma unroll
@@ -904,6 +963,7 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
         }
       }
     }
+  }
   }
   WB_STAMP(3);
   if constexpr (PS) ps_stamp(ps, 3);

@@ -473,6 +473,67 @@ int wbk_cross_fused(WbkCross* t) {
   return P.err;
 }
 
+// launch_dec_attn_fused_rounds (decode_fused.hip): one fused self-attention sublayer step at d = 384 over n_rows live rows, with
+// n_reg (2 or 4) QKV weight rounds held in registers.  The step state is assembled here (st[ST_N] = n_rows, row r has length
+// lens[r] including the new token, no row dead, step parity 0).  x_in / x_out [S][d], pend [KSp][S][d], Wqkv [d][ldqkv],
+// tabs [S][Lmax]: cache slot of position p of row r; Kc / Vc [n_slots][d] (copied in and back: the new token's rows are
+// written), P [n_head][S][d] (copied in and back).
+struct WbkAttnRounds {
+  WbkBuf x_in, pend, pbias, x_out, ln_g, ln_b, Wqkv, bqkv, Kc, Vc, tabs, lens, Wo, P;
+  int64_t S, d, n_head, KSp, ldqkv, Lmax, n_slots, n_rows, ln_inside, n_reg;
+  double ln_eps, scale;
+};
+
+int wbk_attn_fused(WbkAttnRounds* t) {
+  const int64_t S = t->S, d = t->d, H = t->n_head, n = t->n_rows, Lmax = t->Lmax, NS = t->n_slots;
+  if (d != 384 || H * 64 != d || S < 1 || S > 64 || n < 1 || n > S || t->KSp < 0 || t->KSp > 64) return WBK_EARG;
+  if (t->n_reg != 2 && t->n_reg != 4) return WBK_EARG;
+  if (Lmax < 1 || Lmax > 448 || NS < 1 || NS * d >= (1ll << 31)) return WBK_EARG;          // (448: the body's position arrays)
+  if (t->ldqkv < 3 * d || t->ldqkv % 4 || !aligned16(t->Wqkv, 0, 4) || !inside(t->Wqkv, 0, (d - 1) * t->ldqkv + 3 * d, 4)) return WBK_EARG;
+  const int32_t* tb = (const int32_t*)t->tabs.host; const int32_t* ln = (const int32_t*)t->lens.host;
+  if (!tb || !ln || t->tabs.off || t->lens.off || t->tabs.bytes < S * Lmax * 4 || t->lens.bytes < n * 4) return WBK_EARG;
+  std::vector<char> is_new((size_t)NS, 0);
+  for (int64_t r = 0; r < n; r++) {
+    if (ln[r] < 1 || ln[r] > Lmax) return WBK_EARG;
+    for (int64_t p = 0; p < ln[r]; p++) if (tb[r * Lmax + p] < 0 || tb[r * Lmax + p] >= NS) return WBK_EARG;
+    char& nw = is_new[(size_t)tb[r * Lmax + ln[r] - 1]];
+    if (nw) return WBK_EARG;                                                               // (two rows writing one cache row)
+    nw = 1;
+  }
+  if (!inside(t->Kc, 0, NS * d, 4) || !inside(t->Vc, 0, NS * d, 4) || !aligned16(t->Kc, 0, 4) || !aligned16(t->Vc, 0, 4)) return WBK_EARG;
+  if (!inside(t->x_in, 0, S * d, 4) || !inside(t->x_out, 0, S * d, 4) || !inside(t->P, 0, H * S * d, 4) || !aligned16(t->P, 0, 4))
+    return WBK_EARG;
+  if (t->KSp > 0 && (!inside(t->pend, 0, t->KSp * S * d, 4) || !inside(t->pbias, 0, d, 4))) return WBK_EARG;
+  if (!inside(t->ln_g, 0, d, 4) || !inside(t->ln_b, 0, d, 4) || !inside(t->bqkv, 0, 3 * d, 4)) return WBK_EARG;
+  if (!inside(t->Wo, 0, d * d, 4) || !aligned16(t->Wo, 0, 4)) return WBK_EARG;
+
+  const wb::StepLayout lay = wb::make_step_layout((int)S, 1);
+  std::vector<int32_t> st((size_t)lay.total, 0);
+  st[wb::ST_N] = (int32_t)n;
+  for (int64_t r = 0; r < n; r++) st[(size_t)(lay.len + r)] = ln[r];
+  const WbkBuf stb{st.data(), (int64_t)st.size() * 4, 0};
+
+  Pool P;
+  char *dst = upload(P, stb), *dx = upload(P, t->x_in), *dpe = upload(P, t->pend), *dpb = upload(P, t->pbias), *dxo = upload(P, t->x_out);
+  char *dg = upload(P, t->ln_g), *db = upload(P, t->ln_b), *dW = upload(P, t->Wqkv), *dbq = upload(P, t->bqkv);
+  char *dK = upload(P, t->Kc), *dV = upload(P, t->Vc), *dtb = upload(P, t->tabs), *dWo = upload(P, t->Wo), *dP = upload(P, t->P);
+  if (P.err) return P.err;
+  auto at = [](char* p, const WbkBuf& b) -> char* { return p ? p + b.off : nullptr; };
+  wb::AttnFusedArgs a;
+  a.st = (const int*)dst; a.lay = lay; a.S = (int)S; a.d = (int)d; a.n_head = (int)H;
+  a.x_in = (const float*)at(dx, t->x_in); a.pend = t->KSp > 0 ? (const float*)at(dpe, t->pend) : nullptr; a.KSp = (int)t->KSp;
+  a.pbias = t->KSp > 0 ? (const float*)at(dpb, t->pbias) : nullptr; a.x_out = (float*)at(dxo, t->x_out);
+  a.ln_g = (const float*)at(dg, t->ln_g); a.ln_b = (const float*)at(db, t->ln_b); a.ln_eps = (float)t->ln_eps; a.ln_inside = (int)t->ln_inside;
+  a.Wqkv = (const float*)at(dW, t->Wqkv); a.ldqkv = (int)t->ldqkv; a.bqkv = (const float*)at(dbq, t->bqkv); a.scale = (float)t->scale;
+  a.Kc = (float*)at(dK, t->Kc); a.Vc = (float*)at(dV, t->Vc); a.tabs = (const int*)dtb; a.Lmax = (int)Lmax;
+  a.Wo = (const float*)at(dWo, t->Wo); a.P = (float*)at(dP, t->P);
+  int status = wb::launch_dec_attn_fused_rounds(nullptr, a, (int)n, (int)t->n_reg);
+  status = finish(P, status);
+  if (status) return status;
+  download(P, t->x_out, dxo); download(P, t->P, dP); download(P, t->Kc, dK); download(P, t->Vc, dV);
+  return P.err;
+}
+
 const char* wbk_version() { return "whisper_hip kernel test harness 1"; }
 
 }  // extern "C"
