@@ -59,6 +59,13 @@ for k in (0, 1, 2, 5, 3, 4):
         print(f"{nm:<10}{int(cols.sum()):>4}{d(0,1):>8.2f}{d(1,2):>8.2f}{d(2,3):>8.2f}{d(3,4):>8.2f}{d(4,5):>8.2f}{d(5,6):>9.2f}{d(6,7):>8.2f}{d(1,6):>8.2f}{rel_done:>9.2f}{rel_arr:>9.2f}")
 dd = np.diff(step_end) * tick
 print(f"step time (merge arrived -> next merge arrived): mean {np.nanmean(dd):.2f} us, median {np.nanmedian(dd):.2f}, min {np.nanmin(dd):.2f}, max {np.nanmax(dd):.2f}")
+# the step boundary: from the last logits role's "done" of step s to "x folded" (p2) of the attn L0 roles of step s + 1
+a0 = (kind == 0) & (layer == 0) & (row == live_row)
+if a0.any() and (kind == 3).any() and hi - lo > 1:
+    lg_done = np.nanmax(st[lo:hi - 1][:, kind == 3, 6], axis=1)
+    for nm, red in (("first", np.nanmin), ("last", np.nanmax)):
+        edge = (red(st[lo + 1:hi][:, a0, 2], axis=1) - lg_done) * tick
+        print(f"last logits done -> attn L0 p2 ({nm} block of row {live_row}): mean {np.nanmean(edge):.2f} us, median {np.nanmedian(edge):.2f}, min {np.nanmin(edge):.2f}, max {np.nanmax(edge):.2f}")
 print("over the roles of a kind (each role: mean over the steps), us after the step start (merge: of its own step's start):")
 print(f"{'role':<10}{'n':>4}  {'wait passed @  min / median / max':<36}{'done @  min / median / max':<34}")
 for nm, wp, dn, blk in spread:

@@ -432,7 +432,12 @@ struct PersistArgs {
   unsigned tag_base = 0;                      // granule tags of this launch: tag_base + 2 + 3 (e n_layer + l) + sublayer
   const float* ln_g = nullptr; const float* ln_b = nullptr; float ln_eps = 0.f; int ln_inside = 0;
   const float* Et = nullptr; int vocab_ld = 0, V = 0; const float* mask = nullptr;
-  float* tstats = nullptr; int n_tiles = 0;   // [S][n_tiles][2]
+  // tile records [2][S][n_tiles] x 16 bytes {tag, best value, tag, best id} (handoff.h: Rec), double-buffered by step parity,
+  // tagged with the step's final-LN tag; zero-filled when allocated
+  void* tstats = nullptr; int n_tiles = 0;
+  // 1: first-layer self-attention picks the row's next token from the records itself; 0: it waits for the merge role's x row
+  // (WHISPER_HIP_PERSIST_PICK=merge).  Travels by value: not part of the cached setup
+  int pick = 1;
   // merge role: argmax over the tiles, chain bookkeeping, next step's embedding
   int* gctl = nullptr; int* gtok = nullptr; int Lmax = 0, eot = 0;
   const float* E = nullptr; const float* pos = nullptr; void* x0 = nullptr; int* tabs = nullptr;   // x0: granules
@@ -462,6 +467,9 @@ int launch_dec_persist(hipStream_t st, const PersistArgs& a, int grid);
 // seeds the granule copy of the first step's x rows: tag = tag_base + 1 (what the first self-attention blocks expect), and
 // the control block's stop word (ctl: the HX_* words, zeroed on the stream in front of this): HX_STOP = INT_MAX, the decode goes on
 void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned tag, int* ctl);
+// test-only: the pick of the first-layer self-attention role in isolation (one block): the best of `n_tiles` records tagged
+// `tag` -> *out_id (0x7fffffff: no record compares).  ctl: ps_ctl_ints(1, 1) zeroed ints (the sweep's stop / error words)
+void launch_ps_pick_test(hipStream_t st, const void* rec, int n_tiles, unsigned tag, int* ctl, int* out_id);
 
 #if defined(HIPEMU) && !defined(HIPEMU_PROD_GEOMETRY)
 // (functional-model build: three tiles per pass, so that micro models run both rings -- one pass at n_audio_ctx = 400

@@ -263,8 +263,9 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   WB_TRY(s->ps_gpc.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
   WB_TRY(s->ps_gp2.ensure_zeroed(((size_t)NB * S + 8) * d * 8, st));
   WB_TRY(s->ps_gxn.ensure_zeroed(((size_t)S + 8) * d * 8, st));
+  WB_TRY(s->ps_tstats.ensure_zeroed((size_t)2 * S * n_tiles * 16, st));   // tile records, tagged like granules, two step parities
   if (((s->ps_launches + 1) & 0xffffu) == 0) {     // the 16-bit launch count wraps: forget every old tag
-    for (DevMem* b : {&s->ps_gx, &s->ps_gpa, &s->ps_gpc, &s->ps_gp2, &s->ps_gxn}) WB_HIP(hipMemsetAsync(b->p, 0, b->bytes, st));
+    for (DevMem* b : {&s->ps_gx, &s->ps_gpa, &s->ps_gpc, &s->ps_gp2, &s->ps_gxn, &s->ps_tstats}) WB_HIP(hipMemsetAsync(b->p, 0, b->bytes, st));
     s->ps_launches++;
   }
   const unsigned tag_base = ((++s->ps_launches) & 0xffffu) << 16;
@@ -280,7 +281,6 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   const int n_ctl = ps_ctl_ints(S, NL);
   WB_TRY(s->ps_ctl.ensure((size_t)n_ctl * 4));
   WB_TRY(s->ps_dead.ensure((size_t)S * 4));
-  WB_TRY(s->ps_tstats.ensure((size_t)S * n_tiles * 2 * 4));
   // the polled words start at zero; HX_STOP = INT_MAX is written by the seed kernel below
   WB_HIP(hipMemsetAsync(s->ps_ctl.p, 0, (size_t)n_ctl * 4, st));
   WB_HIP(hipMemsetAsync(s->ps_dead.p, 0, (size_t)S * 4, st));
@@ -298,7 +298,11 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   a.x_fin = gxb[(3 * NL) & 1]; a.P2 = s->ps_gp2.p; a.b2_last = m->dec[NL - 1].mlp2.b; a.tag_base = tag_base;
   a.ln_g = m->ln_dec.g; a.ln_b = m->ln_dec.b; a.ln_eps = m->ln_dec.eps; a.ln_inside = m->ln_eps_inside_sqrt;
   a.Et = m->tok_emb_t; a.vocab_ld = m->vocab_ld; a.V = V; a.mask = s->mask.as<float>();
-  a.tstats = s->ps_tstats.as<float>(); a.n_tiles = n_tiles;
+  a.tstats = s->ps_tstats.p; a.n_tiles = n_tiles;
+  // WHISPER_HIP_PERSIST_PICK=merge: first-layer self-attention waits for the merge role's x row (the A/B arm); unset: it picks
+  // the token from the tile records itself.  A word of the launch's arguments: the dealt tables do not depend on it
+  const char* pick_sw = sw::persist_pick();
+  a.pick = pick_sw && !strcmp(pick_sw, "merge") ? 0 : 1;
   a.gctl = s->gctl.as<int>(); a.gtok = s->gtok.as<int>(); a.Lmax = s->Lmax; a.eot = eot;
   a.E = m->tok_emb; a.pos = m->dec_pos; a.x0 = gxb[0]; a.tabs = s->tabs.as<int>(); a.dead = s->ps_dead.as<int>();
   // optional role timeline (developer): WHISPER_HIP_PS_STAMPS=<file> dumps [n_steps][n_roles][3] 100 MHz clock values

@@ -33,6 +33,14 @@ struct PsStep {
   // the necessary bytes, profiles/r03_d_pmc_traffic_tiny_en_30s.json); out = the role found its row dead this step
   bool known_dead = false;
   mutable bool saw_dead = false;
+  // first-layer self-attention picks the row's next token itself (decode_persist.hip, "the step boundary"); pk_rec == null: the
+  // step's x row comes from the merge role, as granules.  pk_rec: the row's tile records of the previous step (n_tiles x 16
+  // bytes, tagged pk_tag); pk_go / pk_go_target: the second word of the pre-wake; pk_E: token embedding, pk_pos: THIS step's
+  // position row.  cross_early: the first layer's cross-attention role wakes later relative to its producers (shorter nap)
+  const void* pk_rec = nullptr; int pk_n_tiles = 0; unsigned pk_tag = 0;
+  const unsigned* pk_go = nullptr; unsigned pk_go_target = 0;
+  const float* pk_E = nullptr; const float* pk_pos = nullptr; int pk_eot = 0;
+  bool cross_early = false;
 };
 constexpr int PS_STAMPS = 8;     // 0 role start, 1 wait passed, 2-5 phases inside the role, 6 done, 7 arrived
 __device__ __forceinline__ void ps_stamp(const PsStep& ps, int k) {
@@ -80,6 +88,52 @@ __device__ __forceinline__ void ps_nap() {
   for (int i = 0; i < UNITS + (WB_PS_NAP_ADJ); i++) __builtin_amdgcn_s_sleep(64);
 #endif
 }
+
+// The row's best tile record (value descending, id ascending: wave_ops.h `better`, a strict total order -- every block gets
+// the id the merge role gets, whatever the reduction's shape).  Thread t owns records t, t + 512, ...; each is re-read until
+// both of its tags are `tag` (handoff.h: Rec), bounded like every sweep.  xch: 16 LDS words nobody else uses until the
+// caller's next barrier.  Returns the id in every thread, 0x7fffffff when no record compares (NaN logits); ends with a
+// barrier -- the caller looks at ps_sweeps_ok(ps) next.  Call with ALL 512 threads.
+constexpr int PS_PICK_NONE = 0x7fffffff;
+#ifdef WB_PS_PICK_NOINLINE
+__device__ __attribute__((noinline)) int ps_pick_token(
+#else
+__device__ __forceinline__ int ps_pick_token(
+#endif
+const void* rec, const int n_tiles, const unsigned tag, const PsStep& ps,
+                                             float* xch, const int tid) {
+  const Buf16 rb(rec);
+  float bv = -INFINITY; int bi = PS_PICK_NONE;
+  unsigned sweeps = 0;
+  for (int t = tid; t < n_tiles;) {                // (one flat loop: a stale record is read again, a fresh one steps on)
+    const Rec q = ld_rec(rb, (uint32_t)t);
+    if (q.t0 == tag && q.t1 == tag) {
+      if (better(q.v, q.id, bv, bi)) { bv = q.v; bi = q.id; }
+      t += 512;
+    } else if (ps_sweep_retry(sweeps, ps)) {
+      *ps.lds_flag = 0;
+      break;
+    }
+  }
+  wave_argmax(bv, bi);
+  int* xid = reinterpret_cast<int*>(xch) + 8;
+  if ((tid & 63) == 0) { xch[tid >> 6] = bv; xid[tid >> 6] = bi; }
+  __syncthreads();
+  float gv = xch[0]; int gi = xid[0];
+#pragma unroll
+  for (int j = 1; j < 8; j++)
+    if (better(xch[j], xid[j], gv, gi)) { gv = xch[j]; gi = xid[j]; }
+  return gi;
+}
+#ifndef WB_PS_PICK_NAP
+#define WB_PS_PICK_NAP 6       // nap units between the pick's pre-wake (the last cross-attention stage has finished) and its sweep
+#endif
+#ifndef WB_PS_CROSS0_NAP
+// nap units of the first layer's cross-attention role behind a picking self-attention role: its pre-wake (merge arrived) now
+// fires ~4.7 us before the attention planes land instead of ~7.5; with 2 units the first sweep started 0.3 us after them
+// (profiles/r21_ps_timeline_tree_nap2.txt against _tree.txt: wait -> p2 5.04 against 4.73 us)
+#define WB_PS_CROSS0_NAP 1
+#endif
 
 // developer probe: tools/decode_probe.cpp builds this file with -DWB_STAMPS and prints the phase timeline of block 0
 #ifdef WB_STAMPS
@@ -795,6 +849,34 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
         if constexpr (NREG == 2) load_cache_tile();  // (four rounds: behind the sweep, below -- the granules need the registers)
       }
 #endif
+      // Layer 0 behind a step that chose its token (ps.pk_rec): the block picks the token itself.  Pre-wake on two words that
+      // are long since true when the records appear (the GO word: every cross-attention role of the previous step has arrived, so
+      // the planes and the stream this role overwrites are read; c_x >= e - 1: the merge role of the step before that has arrived,
+      // so the records' other parity may be rewritten behind this step), a nap, the row's tagged records, the argmax, one round trip
+      // for E[tok] + pos[len] -- the merge role's operands and its one add.  A row that ends (eot, or no finite candidate)
+      // takes the old way below: it waits for the merge role, which has written the dead flag and the stop word by then.
+      float v = 0.f;
+      bool picked = false;
+      if (ps.pk_rec != nullptr && !ps.known_dead) {
+        // (the dead flag comes back with the wait, read by ONE lane: merge(r) of the previous step may be storing it right now,
+        // and threads that read it for themselves could part ways in front of the barriers below.  Either value is right: a row
+        // that is just ending picks eot from its records, or goes straight to the wait for the merge role)
+        const int go = hx_wait_two(ps.pk_go, ps.pk_go_target, ps.ctr, ps.target - 1u, ps.ctl, ps.step, ps.ctr_index, ps.lds_flag,
+                                   ps.dead + (r < n_rows ? r : 0));
+        if (go == 0) return false;
+        ps_stamp(ps, 1);
+        if (r < n_rows && go == 1) {
+          ps_nap<WB_PS_PICK_NAP>();
+          const int tok = ps_pick_token(ps.pk_rec, ps.pk_n_tiles, ps.pk_tag, ps, red, tid);
+          if (!ps_sweeps_ok(ps)) return false;
+          if (tok != PS_PICK_NONE && tok != ps.pk_eot) {
+            // (the position row depends on no token, but a register held across the sweep spills a weight quad: both rows together)
+            v = gld(ps.pk_E + (int64_t)tok * d + c) + gld(ps.pk_pos + c);
+            picked = true;
+          }
+        }
+      }
+      if (!picked) {
       if (!ps_wait(ps)) return false;
       dead = ps.known_dead ? 1 : ld_i<true>(ps.dead + r);
       if (r >= n_rows || dead) { ps.saw_dead = true; return true; }
@@ -803,7 +885,7 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
       const int iplane = a.S * d;
       if (a.KSp > 0) ps_nap<2>();                   // (the previous layer's MLP has only just started)
       constexpr int FP = 4 * DPL;                   // the 4 d / 64 planes of the previous layer's MLP
-      float v = 0.f, accp = a.KSp > 0 ? gld(a.pbias + c) : 0.f;
+      float accp = a.KSp > 0 ? gld(a.pbias + c) : 0.f;
       unsigned sweeps = 0;
       // (a granule that has arrived is not read again: the retries of the last planes are short round trips)
       Gran gx{0u, 0.f}, g[FP];
@@ -831,6 +913,7 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
           break;
         }
         if (ps_sweep_retry(sweeps, ps)) { *ps.lds_flag = 0; break; }
+      }
       }
       xfold = v;
       if (tid < d) hs[tid] = v;
@@ -1271,7 +1354,8 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
       const Buf16 xgb(a.g_x_in), pgb(a.g_pend);
       const uint32_t pvo = (uint32_t)(r * d + c);
       const int iplane = a.S * d;
-      ps_nap<4>();                                  // (the self-attention blocks have only just started)
+      // (the self-attention blocks have only just started; behind a picking first-layer role they are well under way)
+      if (ps.cross_early) ps_nap<WB_PS_CROSS0_NAP>(); else ps_nap<4>();
       constexpr int FP = 8;                         // <= 8 head planes
       float v = 0.f, accp = gld(a.pbias + c);
       unsigned sweeps = 0;

@@ -17,7 +17,10 @@
 // The host deals the roles to the blocks (decode_chain.cpp): a block runs its own list, in dependency order, every step.  The
 // first sublayers' blocks take no logits work (they are back at their wait, weights requested, before the step ends).
 // Dependencies = arrival counters (handoff.h), monotonic within the launch:
-//   attn(0,.,r)  waits for merge(r) of the previous step (its x row)          c_x[r]       >= e
+//   attn(0,.,r)  behind a step that chose its token: waits for that step's tile records of row r (tagged, below);
+//                pre-wake on the GO word of epoch e and on c_x[r] >= e - 1.  Step 0, behind a prompt step, a row that ends,
+//                WHISPER_HIP_PERSIST_PICK=merge: waits for merge(r) of the previous step (its x row)   c_x[r] >= e
+//   cross(0,.,r) pre-wake: merge(r) of the previous step                       c_x[r]       >= e
 //   attn(l,.,r)  waits for every MLP slice of layer l - 1                      c_mlp[l-1]   >= (e + 1) NB
 //   cross(l,.,r) waits for the H attention blocks of its row                   c_attn[l][r] >= (e + 1) H
 //   mlp(l,.)     waits for every cross-attention block of the layer            c_cross[l]   >= (e + 1) H R
@@ -26,6 +29,25 @@
 // Every block's list follows one global dependency order and all blocks are co-resident (the host sizes the grid from
 // the occupancy query), so the smallest unfinished role can always run: no deadlock.  Reuse of the plane
 // buffers across steps is ordered by the same chain (a role arrives only after its last read).
+//
+// The step boundary.  The logits roles leave one 16-byte record {tag, value, tag, id} per (row, tile), tagged with the step's
+// final-LN tag, in the buffer of the step's parity.  attn(0,h,r) of step e sweeps row r's records of step e - 1, takes the argmax
+// (`better`: a strict total order, so every block of the row gets merge(r)'s id), and builds E[tok] + pos[len] itself: two
+// dependent round trips where the merge role's flag, its gather, its arrival and the x-row sweep were six.  merge(r) keeps
+// all of its work (token row, gctl, dead flag, stop word, the x0 granules, the tables); nothing waits for it on this path.
+// Ordering rules the edge keeps:
+//   (a) every block's role list stays a subsequence of the global dependency order (ps_deal_roles is as it was);
+//   (b) attn(0) of step e overwrites the attention planes and the folded stream that the cross-attention roles of step e - 1
+//       read: the GO word of epoch e is stored by the LAST cross-attention arrival of step e - 1, so those reads are over;
+//       cross(0,h,r) of step e writes the stream merge(r) of step e - 1 writes its x0 row into: it keeps its wait on
+//       c_x[r] >= e, so the merge role's stores have drained before it stores;
+//   (c) the records of parity p are rewritten by the logits roles of step e + 1; their readers are attn(0) of step e (ahead
+//       of that write by the chain itself) and merge of step e - 1 (ahead because attn(0) of step e + 1 waited for c_x >= e,
+//       that merge's arrival) -- hence two parities and the c_x word in the pre-wake;
+//   (d) results depend on neither timing nor placement; every spin is bounded (HX_SPIN_LIMIT / HX_SWEEP_LIMIT), a give-up
+//       sets the error word and the session falls back to the graph-replayed chain.
+// A row that ends (its pick is eot, or no record compares) waits for merge(r) as before and finds its dead flag: every
+// downstream role reads the dead flag and the stop word in the order it always did.
 //
 // End of the decode: the merge role of the last window to end stores HX_STOP = first step that must not run; every wait
 // polls that word next to its counter, and a block that sees it leaves the kernel (without arriving).  Rows whose window
@@ -114,7 +136,7 @@ struct LogitsLds {
 };
 template <int MR, int DPL>
 __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int tile0, const int n_t, const PsStep& ps,
-                                               const bool forced, LogitsLds<MR, DPL>& sm) {
+                                               const bool forced, const int par, LogitsLds<MR, DPL>& sm) {
   constexpr int d = 64 * DPL, NT = PS_NT, CT = PS_CT;
   constexpr int NR = d / 16;                        // E^T rows per thread: k = (2 wave + hh) NR + i
   constexpr int EPT = (MR * d + NT - 1) / NT;
@@ -193,10 +215,9 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
 #if defined(WB_PS_DRY)
   // dry build (tools/build_exp.sh dry): the role's tile records without the E^T stream and the GEMV -- token 0-ish every step
   for (int t = 0; t < n_t; t++)
-    if (wave < MR && !((deadm >> wave) & 1) && lane == 0) {
-      float* ts = a.tstats + ((int64_t)wave * a.n_tiles + tile0 + t) * 2;
-      st_f<true>(ts, 0.f);
-      st_f<true>(ts + 1, __int_as_float((tile0 + t) * CT));
+    if (wave < MR && !((deadm >> wave) & 1)) {
+      const int r_u = __builtin_amdgcn_readfirstlane(wave);
+      if (lane == 0) st_rec(Buf16(a.tstats), (uint32_t)((par * a.S + r_u) * a.n_tiles + tile0 + t), ps.tag_in, 0.f, (tile0 + t) * CT);
     }
   return true;
 #endif
@@ -252,11 +273,11 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
       float bvv; int bi;
       if (better(v0, lane, v1, lane + 64)) { bvv = v0; bi = lane; } else { bvv = v1; bi = lane + 64; }
       wave_argmax(bvv, bi);
-      if (lane == 0) {
-        float* ts = a.tstats + ((int64_t)r * a.n_tiles + tile) * 2;
-        st_f<true>(ts, bvv);
-        st_f<true>(ts + 1, __int_as_float(n0 + bi));
-      }
+      // this step's record of (row, tile): parity `par`, tagged with the step's final-LN tag, ONE 16-byte write-through store
+      // (the wave-uniform row is taken by the whole wave, in front of the one-lane branch: a wave operation of lane 0 alone
+      // would meet the other lanes' next one)
+      const int r_u = __builtin_amdgcn_readfirstlane(r);
+      if (lane == 0) st_rec(Buf16(a.tstats), (uint32_t)((par * a.S + r_u) * a.n_tiles + tile), ps.tag_in, bvv, n0 + bi);
     }
   };
   run_tile(w0, tile0);
@@ -295,11 +316,11 @@ __device__ __forceinline__ bool ps_merge_role(const PersistArgs& a, const int r,
     gi = a.forced[e];                               // prompt prefill: the next position holds the next prompt token
   } else {
     float bv = -INFINITY; int bi = 0x7fffffff;
+    // (the counters above say every record of this step is in memory: the tags are the first-layer self-attention roles')
+    const Buf16 recb(a.tstats);
     for (int t = tid; t < a.n_tiles; t += PS_NT) {
-      const float* ts = a.tstats + ((int64_t)r * a.n_tiles + t) * 2;
-      const float v = ld_f<true>(ts);
-      const int id = __float_as_int(ld_f<true>(ts + 1));
-      if (better(v, id, bv, bi)) { bv = v; bi = id; }
+      const Rec q = ld_rec(recb, (uint32_t)(((e & 1) * a.S + r) * a.n_tiles + t));
+      if (better(q.v, q.id, bv, bi)) { bv = q.v; bi = q.id; }
     }
     wave_argmax(bv, bi);
     if (lane == 0) { redv[wave] = bv; redi[wave] = bi; }
@@ -423,6 +444,8 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
       bool ok;
       // granule tags: a stage's planes and folded stream carry tag(e, layer, sublayer); a role consumes tag - 1
       const unsigned tag_l = a.tag_base + 2u + 3u * (unsigned)(e * NL + (role.kind <= PSR_MLP ? role.layer : NL - 1));
+      // step e - 1 chose its token (it was no prompt step) and this step's position row exists: the pick edge
+      const bool pick_e = a.pick != 0 && e >= 1 && e - 1 >= a.n_forced && ps.step < a.Lmax;
       if (role.kind == PSR_ATTN) {
         const AttnFusedArgs la = a.layers[role.layer].attn;
         // layer 0: the merge role's flag (its x row follows as granules); else pre-wake = the previous layer's
@@ -431,6 +454,13 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         else { ps.ctr_index = C_CROSS + role.layer - 1; ps.target = (unsigned)(e + 1) * H * R; }
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_out = tag_l; ps.tag_in = tag_l - 1u;
+        if (role.layer == 0 && pick_e) {             // the step boundary: the role picks the row's token from the records itself
+          ps.pk_rec = static_cast<const char*>(a.tstats) + ((size_t)((e - 1) & 1) * S + role.b) * a.n_tiles * sizeof(Rec);
+          ps.pk_n_tiles = a.n_tiles;
+          ps.pk_tag = a.tag_base + 4u + 3u * (unsigned)((e - 1) * NL + NL - 1);   // the final-LN tag of step e - 1
+          ps.pk_go = cptr(C_GO + (role.b * H + role.a) % PS_NGO); ps.pk_go_target = (unsigned)e;
+          ps.pk_E = a.E; ps.pk_pos = a.pos + (int64_t)ps.step * a.d; ps.pk_eot = a.eot;
+        }
         ok = dec_attn_body<DPL, true, RS>(la, role.a, role.b, ps, lds.attn, i == res_i ? res_buf : nullptr);
         out = C_ATTN + role.layer * S + role.b;
       } else if (role.kind == PSR_CROSS) {
@@ -440,6 +470,7 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         else { ps.ctr_index = C_MLP + role.layer - 1; ps.target = (unsigned)(e + 1) * NB; }
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_out = tag_l + 1u; ps.tag_in = tag_l;
+        ps.cross_early = role.layer == 0 && pick_e;
         ok = dec_cross_body<DPL, true, NP, RS>(la, role.a, role.b, ps, lds.cross, i == res_i ? res_buf : nullptr);
         out = C_CROSS + role.layer;
       } else if (role.kind == PSR_MLP) {
@@ -463,7 +494,7 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         ps.ctr_index = C_GO + (role.layer % PS_NGO); ps.target = (unsigned)(e + 1);
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_in = tag_l + 2u;
-        ok = ps_logits_role<MR, DPL>(a, role.a, role.b, ps, e < a.n_forced, lds.logits);
+        ok = ps_logits_role<MR, DPL>(a, role.a, role.b, ps, e < a.n_forced, e & 1, lds.logits);
         out = C_LOG + (role.layer & 7);
       } else {
         ok = ps_merge_role(a, role.b, e, ps, cptr(C_LOG), n_per_ctr, lds.merge);
@@ -487,6 +518,18 @@ __global__ void ps_seed_kernel(const float* __restrict__ x, int n, void* gx, uns
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl[HX_STOP] = INT_MAX;
   const Buf16 b(gx);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) st_gran(b, (uint32_t)i, tag, x[i]);
+}
+
+// test-only (tools/kernel_harness.cpp: wbk_persist_pick): ps_pick_token as the first-layer self-attention role calls it, alone
+__global__ __launch_bounds__(PS_NT) void ps_pick_test_kernel(const void* rec, int n_tiles, unsigned tag, int* ctl, int* out_id) {
+  __shared__ float xch[16];
+  __shared__ int flag;
+  PsStep ps;
+  ps.ctl = ctl; ps.step = -1; ps.lds_flag = &flag;   // (step -1: the zeroed stop word stops nothing)
+  if (threadIdx.x == 0) flag = 1;
+  __syncthreads();
+  const int tok = ps_pick_token(rec, n_tiles, tag, ps, xch, role_tid<true>());
+  if (threadIdx.x == 0) *out_id = ps_sweeps_ok(ps) ? tok : -1;
 }
 
 template <int DPL, int MR, int NP>
@@ -557,6 +600,10 @@ int dec_persist_max_grid(int device, int d, int n_rows, int max_keys) {
 
 void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned tag, int* ctl) {
   hipLaunchKernelGGL(ps_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, n, gx, tag, ctl);
+}
+
+void launch_ps_pick_test(hipStream_t st, const void* rec, int n_tiles, unsigned tag, int* ctl, int* out_id) {
+  hipLaunchKernelGGL(ps_pick_test_kernel, dim3(1), dim3(PS_NT), 0, st, rec, n_tiles, tag, ctl, out_id);
 }
 
 int launch_dec_persist(hipStream_t st, const PersistArgs& a, int grid) {

@@ -149,6 +149,19 @@ __device__ __forceinline__ void st_gran4(const Buf16& b, uint32_t gran_off, unsi
   u[1] = __float_as_uint(v.z); u[3] = __float_as_uint(v.w);
   __builtin_amdgcn_raw_buffer_store_b128(u, b.r, gran_off * 8u + 16u, 0, 16);
 }
+// A logits tile's record of one row: 16 bytes {tag, best value, tag, best id} = two granules in ONE write-through store (the
+// st_gran4 layout).  The reader takes the record when BOTH tags are the producing step's.
+struct Rec { unsigned t0; float v; unsigned t1; int id; };
+__device__ __forceinline__ Rec ld_rec(const Buf16& b, uint32_t rec_off) {
+  const hx_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(b.r, rec_off * 16u, 0, 16);
+  return Rec{u[0], __uint_as_float(u[1]), u[2], (int)u[3]};
+}
+// (rec_off must be wave-uniform: it rides in the scalar offset -- the storing lane spends no address register)
+__device__ __forceinline__ void st_rec(const Buf16& b, uint32_t rec_off, unsigned tag, float v, int id) {
+  hx_u32x4 u;
+  u[0] = tag; u[1] = __float_as_uint(v); u[2] = tag; u[3] = (unsigned)id;
+  __builtin_amdgcn_raw_buffer_store_b128(u, b.r, 0, rec_off * 16u, 16);
+}
 constexpr unsigned HX_SWEEP_LIMIT = 1u << 20;     // sweeps before a granule wait gives up
 
 // ---- arrival counters ---------------------------------------------------------------------------------------------
@@ -196,6 +209,39 @@ __device__ __forceinline__ bool hx_wait(const unsigned* ctr, unsigned target, co
   const int ok = *lds_flag;
   __syncthreads();                     // (the flag word is reused by the next wait)
   return ok != 0;
+}
+
+// Wait until *c0 >= t0 AND *c1 >= t1 (two words on lines of their own, polled by ONE lane).  Same contract as hx_wait; a
+// give-up names ctr_index.  Returns 0: stopped; else 1 + (*word != 0), `word` read ONCE, by the polling lane, behind the wait:
+// a word that another block may be storing right now (the row's dead flag) reaches every thread with the same value.  A
+// nonzero value stays in *lds_flag (ps_sweeps_ok reads it as "go on").
+__device__ __forceinline__ int hx_wait_two(const unsigned* c0, unsigned t0, const unsigned* c1, unsigned t1, const int* ctl,
+                                           int step, int ctr_index, int* lds_flag, const int* word) {
+  if (threadIdx.x == 0) {
+    int ok = 1;
+    unsigned spins = 0;
+    bool have0 = false;
+    for (;;) {
+      if (!have0) have0 = __hip_atomic_load(c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= t0;
+      if (have0 && __hip_atomic_load(c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= t1) break;
+      if ((spins & 15u) == 15u &&
+          (__hip_atomic_load(ctl + HX_STOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= step ||
+           __hip_atomic_load(ctl + HX_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) { ok = 0; break; }
+      if (++spins > HX_SPIN_LIMIT) {
+        __hip_atomic_store(const_cast<int*>(ctl) + HX_ERR, 1 + ctr_index, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ok = 0;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(2);
+    }
+    if (ok && __hip_atomic_load(ctl + HX_STOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= step) ok = 0;
+    if (ok && __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) ok = 2;
+    *lds_flag = ok;
+  }
+  __syncthreads();
+  const int ok = *lds_flag;
+  __syncthreads();                     // (the flag word is reused by the next wait)
+  return ok;
 }
 
 // Wait until ctr[k HX_LINE] >= target[k] for every k < n (n <= 64): lane k of wave 0 polls counter k, so that the wait costs

@@ -534,6 +534,33 @@ int wbk_attn_fused(WbkAttnRounds* t) {
   return P.err;
 }
 
+// launch_ps_pick_test (decode_persist.hip): the token pick of the persistent kernel's first-layer self-attention role over one
+// row's tile records.  rec: n_tiles records of 16 bytes {tag, value (f32), tag, id (i32)}, 16-byte aligned in its array; every
+// record must carry `tag` twice (a stale record would be waited for: refused here, nothing is launched).  out_id: the id.
+struct WbkPick { WbkBuf rec; int64_t n_tiles, tag, out_id; };
+
+int wbk_persist_pick(WbkPick* t) {
+  const int64_t n = t->n_tiles;
+  if (n < 1 || n > (1 << 20) || t->tag < 1 || t->tag > 0xffffffffll) return WBK_EARG;
+  if (!inside(t->rec, 0, n * 4, 4) || !aligned16(t->rec, 0, 4)) return WBK_EARG;
+  const uint32_t* hr = (const uint32_t*)((const char*)t->rec.host + t->rec.off);
+  for (int64_t i = 0; i < n; i++) if (hr[4 * i] != (uint32_t)t->tag || hr[4 * i + 2] != (uint32_t)t->tag) return WBK_EARG;
+  Pool P;
+  char* drec = upload(P, t->rec);
+  const int n_ctl = wb::ps_ctl_ints(1, 1);
+  void *dctl = nullptr, *dout = nullptr;
+  if (P.ok(hipMalloc(&dctl, (size_t)n_ctl * 4))) { P.dev.push_back(dctl); P.ok(hipMemset(dctl, 0, (size_t)n_ctl * 4)); }
+  if (P.ok(hipMalloc(&dout, 4))) { P.dev.push_back(dout); P.ok(hipMemset(dout, 0xff, 4)); }
+  if (P.err) return P.err;
+  wb::launch_ps_pick_test(nullptr, drec + t->rec.off, (int)n, (unsigned)t->tag, (int*)dctl, (int*)dout);
+  const int status = finish(P, 0);
+  if (status) return status;
+  int id = -1;
+  P.ok(hipMemcpy(&id, dout, 4, hipMemcpyDeviceToHost));
+  t->out_id = id;
+  return P.err;
+}
+
 const char* wbk_version() { return "whisper_hip kernel test harness 1"; }
 
 }  // extern "C"
