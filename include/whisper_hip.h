@@ -497,7 +497,10 @@ int wb_persist_resident_geometry(int32_t n_state, int32_t n_rows, int32_t max_ke
 /* Debug / tests: one step's roles of the persistent greedy kernel as they are dealt to a grid of `grid` blocks (clamped to
  * the roles of a step) -- per role, grouped by block, out_kinds = kind | layer << 8 | row << 16 (kind: 0 self-attention,
  * 1 cross-attention, 2 MLP, 3 logits, 4 merge, 5 final LayerNorm; the encoding of the WHISPER_HIP_PS_STAMPS file) and
- * out_block = its block.  legacy != 0: the dealing of WHISPER_HIP_PERSIST_DEAL=legacy.  Needs no device.  Returns the
+ * out_block = its block.  legacy != 0: the dealing of WHISPER_HIP_PERSIST_DEAL=legacy.  The plan is the one of the `planes`
+ * MLP form (WHISPER_HIP_PERSIST_MLP=planes, and every grid below 4 n_state / 64 blocks); the default two-phase form deals the
+ * same roles to the same blocks without the final-LayerNorm roles, and a block with a last-layer MLP role takes one logits tile
+ * where the others can absorb the rest (WHISPER_HIP_PERSIST_DEAL=log reports that deal).  Needs no device.  Returns the
  * number of roles (at most cap), or a negative status: WB_ERR_SHAPE if no instance serves the shape. */
 int wb_persist_role_plan(int32_t n_layer, int32_t n_head, int32_t n_state, int32_t n_rows, int32_t n_vocab, int32_t grid,
                          int32_t legacy, int32_t* out_kinds, int32_t* out_block, int32_t cap);

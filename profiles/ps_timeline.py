@@ -3,9 +3,12 @@
 Per role kind and layer, over the roles of LIVE rows only (a row whose window has ended skips its attention roles): the
 time from role start to the wait being passed, the phases after the wait, and the arrive; per step, the critical chain.
 Stamp slots: 0 role start, 1 wait passed, 2-5 phases inside the role, 6 done, 7 arrived.  Clock: 100 MHz (10 ns ticks).
-Below the table, for the attn, cross, finln and merge rows: min / median / max OVER THE ROLES of the kind (each role's mean over
+Below the table, for the attn, cross, mlp, finln and merge rows: min / median / max OVER THE ROLES of the kind (each role's mean over
 the steps) of "wait passed @" and "done @" relative to the step start -- a stage whose roles fall in two groups shows here and
 not in a mean -- and, when the file carries role_off behind the stamps (files written since R15), each role's block.
+Then the MLP edges: from the last MLP role's "done" of layer l to "x folded" (p2) of the next layer's self-attention roles (the
+last layer: of the final-LN roles, or of the logits roles where the deal has no final-LN role), the spread of a layer's MLP
+roles' "done" inside a step, and the step time separately for the steps with one, two, three ... live rows.
     python profiles/ps_timeline.py stamps.bin [first_step last_step] [row]"""
 import sys
 
@@ -52,7 +55,7 @@ for k in (0, 1, 2, 5, 3, 4):
         rel_done = np.nanmean((np.nanmax(s[:, :, 6], axis=1) - step_start) * tick)
         rel_arr = np.nanmean((np.nanmax(s[:, :, 7], axis=1) - step_start) * tick)
         nm = names[k] + (f" L{l}" if k < 3 else "")
-        if k in (0, 1, 3, 4, 5):                    # per role: mean over the steps of (stamp - step start)
+        if k in (0, 1, 2, 3, 4, 5):                 # per role: mean over the steps of (stamp - step start)
             wp = np.nanmean((s[:, :, 1] - step_start[:, None]) * tick, axis=0)
             dn = np.nanmean((s[:, :, 6] - step_start[:, None]) * tick, axis=0)
             spread.append((nm, wp, dn, block[cols] if block is not None else None))
@@ -85,3 +88,34 @@ for nm, wp, dn, blk in spread:
     if nm in ("attn L0", "merge", "finln"):
         per = "  ".join((f"b{blk[i]}:" if blk is not None else f"#{i}:") + f"{wp[i]:.2f}/{dn[i]:.2f}" for i in range(len(wp)))
         print(f"{'':<10}per role (block: wait passed @ / done @)  {per}")
+# the MLP edges: last mlp(l) done -> p2 of the consumers; spread of the MLP roles' done inside a step
+def stats(v):
+    return f"mean {np.nanmean(v):.2f} us, median {np.nanmedian(v):.2f}, min {np.nanmin(v):.2f}, max {np.nanmax(v):.2f}"
+n_layer = int(layer[kind == 2].max()) + 1 if (kind == 2).any() else 0
+for l in range(n_layer):
+    m = (kind == 2) & (layer == l)
+    mdone = sel[:, m, 6]
+    if not np.isfinite(mdone).any():
+        continue
+    last_done = np.nanmax(mdone, axis=1)
+    print(f"mlp L{l} done, last - first role inside a step ({int(m.sum())} roles): {stats((last_done - np.nanmin(mdone, axis=1)) * tick)}")
+    if l + 1 < n_layer:
+        cons, cn = (kind == 0) & (layer == l + 1) & (row == live_row), f"attn L{l + 1} p2"
+    elif (kind == 5).any():
+        cons, cn = (kind == 5) & (row == live_row), "finln p2"
+    else:
+        cons, cn = kind == 3, "logits p2"
+    if cons.any() and np.isfinite(sel[:, cons, 2]).any():
+        for nm, red in (("first", np.nanmin), ("last", np.nanmax)):
+            print(f"last mlp L{l} done -> {cn} ({nm} block): {stats((red(sel[:, cons, 2], axis=1) - last_done) * tick)}")
+# step time by the number of live rows (a row is live in a step when a first-layer self-attention role of it folded its x row)
+a0all = (kind == 0) & (layer == 0)
+if a0all.any() and hi - lo > 1:
+    rows = sorted(set(row[a0all]))
+    n_live = np.zeros(hi - lo, dtype=int)
+    for r in rows:
+        n_live += np.isfinite(sel[:, a0all & (row == r), 2]).any(axis=1)
+    for n in sorted(set(n_live[1:]), reverse=True):
+        v = dd[n_live[1:] == n]
+        if len(v) and np.isfinite(v).any():
+            print(f"step time with {n} live row(s) ({len(v)} steps): {stats(v)}")

@@ -406,7 +406,10 @@ int launch_dec_skinny_gemm(hipStream_t st, const SkinnyArgs& a);
 // cross-attention block (head, row), MLP block (64 hidden units), logits tile (128 vocabulary columns), merge (row)),
 // streams each role's weights BEFORE it waits for the arrival counter of the role's producers, and publishes its output
 // planes with write-through stores (handoff.h).  No kernel boundary, no grid barrier, fixed summation orders.
-struct PsLayerArgs { AttnFusedArgs attn; CrossFusedArgs cross; MlpFusedArgs mlp; };
+struct PsLayerArgs {
+  AttnFusedArgs attn; CrossFusedArgs cross; MlpFusedArgs mlp;
+  const float* mlp_b2 = nullptr;              // [d]: bias of the layer's second MLP matrix (two-phase MLP roles add it themselves)
+};
 enum { PSR_ATTN = 0, PSR_CROSS = 1, PSR_MLP = 2, PSR_LOGITS = 3, PSR_MERGE = 4, PSR_FINLN = 5 };
 struct PsRole { int kind, layer, a, b; };     // a: head / hidden slice / first tile, b: row (logits: tiles of the role; layer: its ordinal)
 constexpr int PS_MAX_FORCED = 8;
@@ -426,9 +429,10 @@ struct PersistArgs {
   // forced[e] (the rest of the prompt, transcribe.rs:203) -- and skip the logits work
   int n_forced = 0; int forced[PS_MAX_FORCED] = {0, 0, 0, 0, 0, 0, 0, 0};
   int mask_until_len = 0;                     // special-token mask while len <= this (transcribe.rs:271-275)
-  // logits role: LN(x_fin + b2 + sum P2) . E^T tile -> (best value, best id) per row and tile (x_fin, P2: granules)
+  // logits role: LN(row) . E^T tile -> (best value, best id) per row and tile.  mlp2: row = x_fin, the last layer's finished rows
+  // (granules), normalised by the role itself; else the final-LN role folds x_fin + b2 + sum P2 and leaves LN of it in g_xn
   const void* x_fin = nullptr; const void* P2 = nullptr; const float* b2_last = nullptr;
-  void* g_xn = nullptr;                       // [S][d] granules: ln(x + last MLP), written once per row by the final-LN role
+  void* g_xn = nullptr;                       // planes form only: [S][d] granules ln(x + last MLP), once per row by the final-LN role
   unsigned tag_base = 0;                      // granule tags of this launch: tag_base + 2 + 3 (e n_layer + l) + sublayer
   const float* ln_g = nullptr; const float* ln_b = nullptr; float ln_eps = 0.f; int ln_inside = 0;
   const float* Et = nullptr; int vocab_ld = 0, V = 0; const float* mask = nullptr;
@@ -438,6 +442,12 @@ struct PersistArgs {
   // 1: first-layer self-attention picks the row's next token from the records itself; 0: it waits for the merge role's x row
   // (WHISPER_HIP_PERSIST_PICK=merge).  Travels by value: not part of the cached setup
   int pick = 1;
+  // 1: the MLP role runs in two phases (decode_persist.hip, "the MLP edge"): its 64 hidden values per row go to g_hid, every MLP
+  // block then finishes 16 columns of the residual row, and the logits roles apply the final LayerNorm to that row themselves
+  // (the deal holds no final-LN role); 0: 4 d / 64 partial planes per layer and a final-LN role (WHISPER_HIP_PERSIST_MLP=planes).
+  // Travels by value; the dealt roles depend on it (part of the cached setup's key)
+  int mlp2 = 1;
+  void* g_hid = nullptr;                      // [S][4 d] granules: GELU(hidden) of the layer whose MLP roles are running
   // merge role: argmax over the tiles, chain bookkeeping, next step's embedding
   int* gctl = nullptr; int* gtok = nullptr; int Lmax = 0, eot = 0;
   const float* E = nullptr; const float* pos = nullptr; void* x0 = nullptr; int* tabs = nullptr;   // x0: granules
@@ -448,15 +458,19 @@ struct PersistArgs {
 // policy decides where the final-LN, logits and merge roles go.  PS_DEAL_SLACK keeps merge(r) and finln(r) off the blocks
 // that hold a first-layer self- or cross-attention role (they must be back at their wait, operands requested, before the
 // step ends); PS_DEAL_LEGACY puts them on the least loaded blocks.  Every block's list is a subsequence of the one global
-// dependency order (layer roles by layer and sublayer, finln, logits, merge).
+// dependency order (layer roles by layer and sublayer, finln, logits, merge).  Two-phase MLP roles (PersistArgs::mlp2) also wait
+// for the other MLP roles of their own layer: that form needs nb_mlp <= grid, which puts those roles on different blocks.
 enum { PS_DEAL_SLACK = 0, PS_DEAL_LEGACY = 1 };
 struct PsDeal {
   std::vector<PsRole> roles;                  // grouped by block
   std::vector<int> role_off;                  // [grid + 1]
   std::vector<int> res_role;                  // [grid]: PersistArgs::res_role (all -1 with res_on false)
   int n_lg = 0, n_res = 0;
+  std::vector<int> tail_block;                // [n_rows]: the block kept for row r's final-LN role (it takes no logits tiles)
 };
-PsDeal ps_deal_roles(int n_layer, int n_head, int n_rows, int nb_mlp, int n_tiles, int grid, int policy, bool res_on);
+// finln false: no final-LN roles (the logits roles normalise the rows themselves); everything else is dealt as with them
+PsDeal ps_deal_roles(int n_layer, int n_head, int n_rows, int nb_mlp, int n_tiles, int grid, int policy, bool res_on,
+                     bool finln = true);
 int ps_ctl_ints(int S, int n_layer);
 bool dec_persist_supported(int d, int n_rows, int max_keys);
 int dec_persist_resident_slots(int d, int n_rows, int max_keys);   // resident float4 slots per thread; 0: nothing useful fits
@@ -470,6 +484,20 @@ void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned ta
 // test-only: the pick of the first-layer self-attention role in isolation (one block): the best of `n_tiles` records tagged
 // `tag` -> *out_id (0x7fffffff: no record compares).  ctl: ps_ctl_ints(1, 1) zeroed ints (the sweep's stop / error words)
 void launch_ps_pick_test(hipStream_t st, const void* rec, int n_tiles, unsigned tag, int* ctl, int* out_id);
+// test-only: ONE layer's MLP roles of the persistent kernel in the two-phase form, alone: 4 d / 64 co-resident blocks, block j =
+// hidden slice j, up to 4 rows (d = 128 or 384).  a: the role's arguments with the granule pointers set (g_x_in and g_pend carry
+// tag_in; the finished rows land in g_x_out with tag_in + 1); dead [S]: != 0 masks a row; g_hid: (S + 2) x 4 d zeroed granules;
+// b2 [d]; ctl: ps_ctl_ints(1, 1) zeroed ints.  -1: the shape is not served or the cooperative launch was refused
+struct PsMlp2TestArgs {
+  MlpFusedArgs a; int n_rows = 0; const int* dead = nullptr; void* g_hid = nullptr; const float* b2 = nullptr; unsigned tag_in = 0;
+  int* ctl = nullptr;
+};
+int launch_ps_mlp2_test(hipStream_t st, const PsMlp2TestArgs& t);
+// test-only: ONE logits role of the persistent kernel over its first n_t tiles (n_t = 1 or 2), a block of its own, up to 4 rows (d =
+// 128 or 384).  a.mlp2 = 1: the role sweeps a.x_fin (rows tagged `tag`) and normalises them itself; a.mlp2 = 0: a second block runs the
+// final-LN role of every row (a.nb_mlp planes of a.P2 folded onto a.x_fin + a.b2_last -> a.g_xn), then the logits role on a.g_xn.
+// Records land in a.tstats [S][a.n_tiles], tagged `tag`.  a.ctl: ps_ctl_ints(1, 1) zeroed ints; a.dead [S].  -1: shape not served
+int launch_ps_logits_test(hipStream_t st, const PersistArgs& a, unsigned tag, int n_t);
 
 #if defined(HIPEMU) && !defined(HIPEMU_PROD_GEOMETRY)
 // (functional-model build: three tiles per pass, so that micro models run both rings -- one pass at n_audio_ctx = 400

@@ -39,7 +39,7 @@ static int ps_pin_ensure(wb_session* s, size_t ints) {
 // finln(r) (that role requests only LayerNorm parameters before its wait, so starting it at the step boundary costs
 // nothing), else to a block that is not early and holds no logits role, else to any block that is not early; finln
 // prefers blocks that are not early in the same way.  Only where every block is early (small grids) the least loaded ones.
-PsDeal ps_deal_roles(int NL, int H, int W, int NB, int n_tiles, int grid, int policy, bool res_on) {
+PsDeal ps_deal_roles(int NL, int H, int W, int NB, int n_tiles, int grid, int policy, bool res_on, bool finln) {
   std::vector<PsRole> lr;                            // the layer roles in dependency order
   for (int l = 0; l < NL; l++) {
     for (int r = 0; r < W; r++) for (int h = 0; h < H; h++) lr.push_back(PsRole{PSR_ATTN, l, h, r});
@@ -73,16 +73,37 @@ PsDeal ps_deal_roles(int NL, int H, int W, int NB, int n_tiles, int grid, int po
     std::vector<int> order(grid);
     for (int b = 0; b < grid; b++) order[b] = b;
     by_load(order);
-    for (int r = 0; r < W; r++) { fin_block[r] = order[r % grid]; deal[fin_block[r]].push_back(PsRole{PSR_FINLN, 0, 0, r}); is_fin[fin_block[r]] = 1; }
+    // (without final-LN roles -- the logits roles normalise -- the same blocks stay free of logits tiles for the merge roles)
+    for (int r = 0; r < W; r++) {
+      fin_block[r] = order[r % grid];
+      if (finln) deal[fin_block[r]].push_back(PsRole{PSR_FINLN, 0, 0, r});
+      is_fin[fin_block[r]] = 1;
+    }
   }
   if ((int)cand.size() > 2 * W) cand.erase(std::remove_if(cand.begin(), cand.end(), [&](int b) { return is_fin[b] != 0; }), cand.end());
   std::stable_sort(cand.begin(), cand.end(), [&](int x, int y) { return deal[x].size() < deal[y].size(); });
-  const int tpb = (n_tiles + (int)cand.size() - 1) / (int)cand.size();
-  const int n_lg = (n_tiles + tpb - 1) / tpb;
+  int tpb = (n_tiles + (int)cand.size() - 1) / (int)cand.size();
+  // Without final-LN roles the rows are there as soon as the last layer's MLP roles have finished, and a block that holds one of
+  // those requests its E^T tiles only then: with two tiles its wait's poll queued ~5 us behind them and it finished the step's
+  // logits 6 us after everybody else (profiles/r22_ps_timeline_tree_deal0.txt).  Such a block takes ONE tile where the others
+  // can absorb the rest without a longer run (bench shape: 24 x 1 + 191 x 2 = 406 tiles on 215 of the 217 eligible blocks).
+  std::vector<char> late(grid, 0);
+  int n_late = 0;
+  if (!finln && tpb > 1) {
+    for (int b : cand) {
+      for (const PsRole& r : deal[b]) late[b] |= r.kind == PSR_MLP && r.layer == NL - 1;
+      n_late += late[b];
+    }
+    const int n_other = (int)cand.size() - n_late;
+    if (n_late == 0 || n_other <= 0 || (n_tiles - n_late + n_other - 1) / n_other > tpb) { std::fill(late.begin(), late.end(), 0); n_late = 0; }
+  }
   std::vector<char> has_lg(grid, 0);
-  for (int q = 0; q < n_lg; q++) {
-    deal[cand[q]].push_back(PsRole{PSR_LOGITS, q, q * tpb, std::min(tpb, n_tiles - q * tpb)});
+  int n_lg = 0;
+  for (int q = 0, t0 = 0; q < (int)cand.size() && t0 < n_tiles; q++) {
+    const int n = std::min(late[cand[q]] ? 1 : tpb, n_tiles - t0);
+    deal[cand[q]].push_back(PsRole{PSR_LOGITS, n_lg++, t0, n});
     has_lg[cand[q]] = 1;
+    t0 += n;
   }
   // merge (one per row)
   {
@@ -100,6 +121,7 @@ PsDeal ps_deal_roles(int NL, int H, int W, int NB, int n_tiles, int grid, int po
   }
   PsDeal out;
   out.n_lg = n_lg;
+  out.tail_block = fin_block;
   out.role_off.assign(grid + 1, 0);
   for (int b = 0; b < grid; b++) {
     out.role_off[b] = (int)out.roles.size();
@@ -121,10 +143,21 @@ PsDeal ps_deal_roles(int NL, int H, int W, int NB, int n_tiles, int grid, int po
   return out;
 }
 
-// WHISPER_HIP_PERSIST_DEAL=log: where the roles of the step's tail went, one line per built setup
-static void ps_deal_log(const PsDeal& deal, int grid) {
+// Blocks of the persistent launch of this session: what is co-resident, but never more than one step has roles.  The one place
+// the grid is computed: the dealing and the choice of the MLP form (two phases need nb_mlp <= grid) both rest on it.
+static int ps_grid_blocks(const wb_session* s) {
+  const wb_dims& D = s->m->dims;
+  const int NB = dec_mlp_fused_planes(D.n_text_state), n_tiles = (D.n_vocab + 127) / 128;
+  const int n_layer_roles = D.n_text_layer * (2 * s->W * D.n_text_head + NB);
+  return std::max(1, std::min(s->ps_grid, n_layer_roles + n_tiles + 2 * s->W));
+}
+
+// WHISPER_HIP_PERSIST_DEAL=log: where the roles of the step's tail went and which MLP form runs, one line per built setup
+static void ps_deal_log(const PsDeal& deal, int grid, bool finln) {
   std::string where[2];
   int n_lg_blocks = 0;
+  // (two-phase form, no final-LN roles: "finln on" lists the blocks kept free of logits tiles for the rows' merge roles)
+  if (!finln) for (int b : deal.tail_block) where[1] += (where[1].empty() ? "" : ",") + std::to_string(b);
   for (int b = 0; b < grid; b++) {
     bool lg = false;
     for (int i = deal.role_off[b]; i < deal.role_off[b + 1]; i++) {
@@ -137,7 +170,8 @@ static void ps_deal_log(const PsDeal& deal, int grid) {
     }
     n_lg_blocks += lg;
   }
-  fprintf(stderr, "persist deal: merge on blocks %s; finln on %s; logits blocks %d\n", where[0].c_str(), where[1].c_str(), n_lg_blocks);
+  fprintf(stderr, "persist deal: merge on blocks %s; finln on %s; logits blocks %d; mlp form %s\n", where[0].c_str(), where[1].c_str(),
+          n_lg_blocks, finln ? "planes (final-LN roles)" : "two-phase (no final-LN role: final LayerNorm inside the logits roles)");
 }
 
 // The launch setup of the persistent kernel: the per-layer argument blocks -- exactly what enqueue_step hands the fused
@@ -147,7 +181,7 @@ static void ps_deal_log(const PsDeal& deal, int grid) {
 // uploads it once: it is kept under a key that names everything it was built from.  WHISPER_HIP_PERSIST_SETUP=0: built and
 // uploaded on every call (A/B runs); "log": one line per launch on stderr ("0log": both).  *built: this call built it (and
 // waited for the upload: the staging is on the stack).
-static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
+static int ps_setup_ensure(wb_session* s, bool res_on, bool mlp2, bool* built) {
   wb_model* m = s->m;
   const wb_dims& D = m->dims;
   const int d = D.n_text_state, H = D.n_text_head, NL = D.n_text_layer, V = D.n_vocab, S = s->S, W = s->W;
@@ -158,8 +192,7 @@ static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
   const size_t pool = (size_t)s->Lmax * S;
   const int ldkv = 2 * d;
   const int n_pass = s->maxC > CROSS_FUSED_MAX_C ? 2 : 1;
-  const int n_layer_roles = NL * (2 * W * H + NB);
-  const int grid = std::max(1, std::min(s->ps_grid, n_layer_roles + n_tiles + 2 * W));
+  const int grid = ps_grid_blocks(s);
   const char* deal_sw = sw::persist_deal();
   const int policy = deal_sw && !strcmp(deal_sw, "legacy") ? PS_DEAL_LEGACY : PS_DEAL_SLACK;
   auto up = [](const void* p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); };
@@ -167,7 +200,7 @@ static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
       s->model_uid, (uint64_t)W, (uint64_t)S, (uint64_t)s->Lmax, (uint64_t)grid, (uint64_t)n_tiles, (uint64_t)n_pass,
       (uint64_t)s->enc_rows, (uint64_t)res_on, (uint64_t)m->ln_eps_inside_sqrt, up(s->state.p), up(s->x.p), up(s->P2.p),
       up(s->Pa.p), up(s->Pc.p), up(s->kc.p), up(s->vc.p), up(s->tabs.p), up(s->ckv.p), up(s->win_meta.p), up(s->ps_gx.p),
-      up(s->ps_gpa.p), up(s->ps_gpc.p), up(s->ps_gp2.p), up(s->ps_gxn.p), (uint64_t)policy};
+      up(s->ps_gpa.p), up(s->ps_gpc.p), up(s->ps_gp2.p), up(s->ps_gxn.p), (uint64_t)policy, (uint64_t)mlp2};
   const char* sw_setup = sw::persist_setup();
   const bool cache_on = !(sw_setup && sw_setup[0] == '0');
   *built = !(cache_on && !s->ps_setup_key.empty() && s->ps_setup_key == key);
@@ -207,11 +240,12 @@ static int ps_setup_ensure(wb_session* s, bool res_on, bool* built) {
     ma.ln_g = b.ln3.g; ma.ln_b = b.ln3.b; ma.ln_eps = b.ln3.eps; ma.ln_inside = m->ln_eps_inside_sqrt;
     ma.W1 = b.mlp1.w; ma.ld1 = b.mlp1.n; ma.b1 = b.mlp1.b; ma.W2 = b.mlp2.w; ma.P = s->P2.as<float>();
     ma.g_x_in = gxb[xi]; ma.g_pend = s->ps_gpc.p; ma.g_x_out = gxb[xi ^ 1]; ma.g_P = s->ps_gp2.p;
+    la[l].mlp_b2 = b.mlp2.b;
     xi ^= 1;
   }
   // ---- one step's roles, dealt to the blocks: every block runs its own list, in dependency order, every step ----
-  PsDeal deal = ps_deal_roles(NL, H, W, NB, n_tiles, grid, policy, res_on);
-  if (deal_sw && !strcmp(deal_sw, "log")) ps_deal_log(deal, grid);
+  PsDeal deal = ps_deal_roles(NL, H, W, NB, n_tiles, grid, policy, res_on, !mlp2);
+  if (deal_sw && !strcmp(deal_sw, "log")) ps_deal_log(deal, grid, !mlp2);
   std::vector<PsRole>& roles = deal.roles;
   const std::vector<int>&role_off = deal.role_off, &res_role = deal.res_role;
   const int n_lg = deal.n_lg, n_res = deal.n_res;
@@ -261,11 +295,24 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   WB_TRY(s->ps_gx.ensure_zeroed(((size_t)2 * S + 8) * d * 8, st));
   WB_TRY(s->ps_gpa.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
   WB_TRY(s->ps_gpc.ensure_zeroed(((size_t)H * S + 8) * d * 8, st));
-  WB_TRY(s->ps_gp2.ensure_zeroed(((size_t)NB * S + 8) * d * 8, st));
-  WB_TRY(s->ps_gxn.ensure_zeroed(((size_t)S + 8) * d * 8, st));
+  // WHISPER_HIP_PERSIST_MLP=planes: the MLP roles leave 4 d / 64 partial planes per layer and a final-LN role folds the last
+  // layer's (the A/B arm); unset: two-phase MLP roles, final LayerNorm inside the logits roles.  The dealt roles depend on it.
+  // Phase 2 of an MLP role waits for the hidden values of ALL 4 d / 64 MLP roles of its layer, so those must sit on different
+  // blocks (layer role i is dealt to block i % grid: they do when the grid has at least that many blocks).  On a smaller grid a
+  // block would wait for a role further down its own list: the planes form, whose roles depend on earlier stages only
+  // (WHISPER_HIP_PERSIST_DEAL=log names the form that runs).
+  const char* mlp_sw = sw::persist_mlp();
+  const bool mlp2 = !(mlp_sw && !strcmp(mlp_sw, "planes")) && ps_grid_blocks(s) >= NB;
+  if (mlp2) {
+    WB_TRY(s->ps_ghid.ensure_zeroed(((size_t)S + 2) * 4 * d * 8, st));
+  } else {                                         // (the planes and the final-LN rows exist in the planes form only)
+    WB_TRY(s->ps_gp2.ensure_zeroed(((size_t)NB * S + 8) * d * 8, st));
+    WB_TRY(s->ps_gxn.ensure_zeroed(((size_t)S + 8) * d * 8, st));
+  }
   WB_TRY(s->ps_tstats.ensure_zeroed((size_t)2 * S * n_tiles * 16, st));   // tile records, tagged like granules, two step parities
   if (((s->ps_launches + 1) & 0xffffu) == 0) {     // the 16-bit launch count wraps: forget every old tag
-    for (DevMem* b : {&s->ps_gx, &s->ps_gpa, &s->ps_gpc, &s->ps_gp2, &s->ps_gxn, &s->ps_tstats}) WB_HIP(hipMemsetAsync(b->p, 0, b->bytes, st));
+    for (DevMem* b : {&s->ps_gx, &s->ps_gpa, &s->ps_gpc, &s->ps_gp2, &s->ps_gxn, &s->ps_ghid, &s->ps_tstats})
+      if (b->p && b->bytes) WB_HIP(hipMemsetAsync(b->p, 0, b->bytes, st));
     s->ps_launches++;
   }
   const unsigned tag_base = ((++s->ps_launches) & 0xffffu) << 16;
@@ -274,7 +321,7 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   const char* res_sw = sw::persist_resident();
   const bool res_on = !(res_sw && res_sw[0] == '0') && dec_persist_resident_slots(d, W, s->maxC) > 0;
   bool built = false;
-  WB_TRY(ps_setup_ensure(s, res_on, &built));
+  WB_TRY(ps_setup_ensure(s, res_on, mlp2, &built));
   const std::vector<PsRole>& roles = s->ps_roles_host;
   const int grid = s->ps_setup_grid, n_res = s->ps_setup_n_res;
   if (res_sw && !strcmp(res_sw, "log")) fprintf(stderr, "persist resident blocks: %d of %d\n", n_res, grid);
@@ -295,6 +342,7 @@ static int run_persistent_chain(wb_session* s, int eot, int max_depth, int mask_
   a.n_forced = n_forced;
   for (int i = 0; i < n_forced; i++) a.forced[i] = forced[i];
   a.g_xn = s->ps_gxn.p;
+  a.mlp2 = mlp2 ? 1 : 0; a.g_hid = s->ps_ghid.p;
   a.x_fin = gxb[(3 * NL) & 1]; a.P2 = s->ps_gp2.p; a.b2_last = m->dec[NL - 1].mlp2.b; a.tag_base = tag_base;
   a.ln_g = m->ln_dec.g; a.ln_b = m->ln_dec.b; a.ln_eps = m->ln_dec.eps; a.ln_inside = m->ln_eps_inside_sqrt;
   a.Et = m->tok_emb_t; a.vocab_ld = m->vocab_ld; a.V = V; a.mask = s->mask.as<float>();

@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "decode.h"
 #include "handoff.h"
 #include "wave_ops.h"
@@ -41,6 +43,10 @@ struct PsStep {
   const unsigned* pk_go = nullptr; unsigned pk_go_target = 0;
   const float* pk_E = nullptr; const float* pk_pos = nullptr; int pk_eot = 0;
   bool cross_early = false;
+  // two-phase MLP role (dec_mlp_body, "two phases"): mlp_hid = the layer's hidden values as granules [S][4 d], null = the role
+  // leaves its partial plane as before; mlp_b2 = the bias of the second matrix
+  void* mlp_hid = nullptr; const float* mlp_b2 = nullptr;
+  bool x_late = false;           // self-attention: the x row is the previous layer's MLP roles' (it lands a stage behind the pre-wake)
 };
 constexpr int PS_STAMPS = 8;     // 0 role start, 1 wait passed, 2-5 phases inside the role, 6 done, 7 arrived
 __device__ __forceinline__ void ps_stamp(const PsStep& ps, int k) {
@@ -414,6 +420,20 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
   float g_own = 0.f, b_own = 0.f;
   float b1v;
   int deadm = 0;                                   // (persistent mode) bit r: row r takes no part (its window has ended)
+  // Two phases (persistent mode, ps.mlp_hid set).  As it stands above, every block leaves a full-width partial of hid . W2 and
+  // every consumer block re-sums 4 d / 64 planes (77 KB per block at d = 384).  Instead: block j publishes its 64 hidden values
+  // per live row as granules (ps.mlp_hid, [S][4 d], tagged tag_out), sweeps ALL 4 d hidden values of the live rows, and
+  // finishes the d / NB = 16 residual columns [16 j, 16 j + 16): its W2 operand is that 16-column strip of all 4 d rows (the
+  // same bytes, requested before the wait like the slice).  The sums are the ones the planes went through, operand for operand:
+  // thread (chain = tid / 4, cq = tid % 4), chain = (slice j', row group g), runs the FMA chain of rows j' 64 + g RPG + i,
+  // i ascending from 0, for a float4 of columns; the groups of a slice sit 4 lanes apart and are added g = 0, + 1, + 2, ...
+  // (lane exchange); then per (row, column): b2, + P_j' for j' ascending, and x + that -- what the consumers' folds computed.
+  constexpr int NB2 = 4 * DPL, NCH = NB2 * G, CB = d / NB2, HD = 4 * d;       // slices, chains per column, columns per block
+  static_assert(!PS || (CB == 16 && 4 * NCH <= NT && (MR * HD) % NT == 0 && (MR & (MR - 1)) == 0), "two-phase geometry");
+  bool two = false;
+  if constexpr (PS) two = ps.mlp_hid != nullptr;
+  const int ch2 = min(tid >> 2, NCH - 1), cq = tid & 3;
+  float b2v = 0.f, xown = 0.f;
   {
     int off[EPT], col[EPT];
 #pragma unroll
@@ -443,6 +463,9 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
       }
       {
         const float* wp = a.W2 + (int64_t)(j0 + jb) * d + cf * 4;
+        if constexpr (PS) {                          // two phases: rows chain RPG + i of the block's 16-column strip
+          if (two) { wp = a.W2 + (int64_t)(ch2 * RPG) * d + jblk * CB + cq * 4; b2v = gld(ps.mlp_b2 + jblk * CB + (tid & (CB - 1))); }
+        }
 #pragma unroll
         for (int i = 0; i < RPG; i++) w2[i] = ld_w4(wp + (int64_t)i * d);
       }
@@ -584,10 +607,18 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
   if constexpr (PS) n_rows = ps.n_rows; else n_rows = min(MR, a.st[ST_N] - a.row0);   // (row group: rows [row0, row0 + MR))
   if (n_rows <= 0) return true;                    // chained decode, every window finished / an empty row group (block-uniform)
   WB_STAMP(1);
+  if constexpr (PS) ps_stamp(ps, 2);        // (timeline slots 2-5: fold done, LN + fc1 done, GELU done, output stored)
   __syncthreads();
   if constexpr (PS) { if (!ps_sweeps_ok(ps)) return false; }
+  // (two phases: the x of this block's own 16 columns, before the row's LDS copy is reused for the slices' partial sums)
+  if constexpr (PS) { if (two) xown = hs[(tid >> 4) & (MR - 1)][jblk * CB + (tid & (CB - 1))]; }
 #if defined(WB_PS_DRY)
   if constexpr (PS) {                                // dry build: publish what the role publishes (zeros), nothing else
+    if (two) {
+      if (tid < MR * CB && (tid >> 4) < n_rows && !((deadm >> (tid >> 4)) & 1))
+        st_gran(Buf16(a.g_x_out), (uint32_t)((tid >> 4) * d + jblk * CB + (tid & (CB - 1))), ps.tag_out, xown);
+      return true;
+    }
     if (jg == 0) {
       const Buf16 pgo(a.g_P);
 #pragma unroll
@@ -648,16 +679,113 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
     for (int r = 0; r < MR; r++)
       *reinterpret_cast<float4*>(&red[wave][r][c4]) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
   }
+  if constexpr (PS) ps_stamp(ps, 3);
   __syncthreads();
   if (tid < MR * HS) {
     const int r = tid >> 6, c = tid & 63;
     float v = 0.f;
 #pragma unroll
     for (int w8 = 0; w8 < 8; w8++) v += red[w8][r][c];                  // wave order fixed
-    hid[r][c] = gelu_erf_f(v + b1v);                                    // mod.rs:377-378
+    const float hval = gelu_erf_f(v + b1v);                             // mod.rs:377-378
+    bool pub = false;
+    if constexpr (PS) pub = two;
+    if (pub) {                                                          // (a wave = a row: the branch is wave-uniform)
+      if (!((deadm >> r) & 1)) st_gran(Buf16(ps.mlp_hid), (uint32_t)(r * HD + j0 + c), ps.tag_out, hval);
+    } else {
+      hid[r][c] = hval;
+    }
+  }
+  if constexpr (PS) {
+    if (two) {
+      ps_stamp(ps, 4);
+      // every hidden value of the live rows: MR 4 d granules, re-read until each carries this stage's tag (the block's own
+      // 64 per row come back the same way)
+      constexpr int EPH = MR * HD / NT, CHK = EPH <= 16 ? EPH : EPH / 2;
+      static_assert(EPH % CHK == 0, "sweep chunks");
+      float hv[EPH];
+      {
+        const Buf16 hgb(ps.mlp_hid);
+        unsigned sweeps = 0;
+        bool bad = false;
+#pragma unroll
+        for (int c0 = 0; c0 < EPH; c0 += CHK) {
+          Gran g[CHK];
+          bool rd[CHK];
+#pragma unroll
+          for (int i = 0; i < CHK; i++) { g[i] = Gran{0u, 0.f}; rd[i] = ((deadm >> ((tid + NT * (c0 + i)) / HD)) & 1) != 0; }
+          while (!bad) {
+#pragma unroll
+            for (int i = 0; i < CHK; i++)
+              if (!rd[i] && g[i].tag != ps.tag_out) g[i] = ld_gran(hgb, (uint32_t)(tid + NT * (c0 + i)), 0u);
+            bool ok = true;
+#pragma unroll
+            for (int i = 0; i < CHK; i++) ok &= rd[i] || g[i].tag == ps.tag_out;
+            if (ok) break;
+            if (ps_sweep_retry(sweeps, ps)) { *ps.lds_flag = 0; bad = true; }
+          }
+#pragma unroll
+          for (int i = 0; i < CHK; i++) hv[c0 + i] = rd[i] ? 0.f : g[i].v;
+        }
+      }
+      // red / hid / obuf are one contiguous run of floats, free from here on (behind the barrier: the GELU threads have read
+      // red): the hidden rows [MR][4 d] go there
+      using ML = MlpLds<MR, DPL, REC>;
+      static_assert(offsetof(ML, hid) == offsetof(ML, red) + sizeof(ML::red) && offsetof(ML, obuf) == offsetof(ML, hid) + sizeof(ML::hid) &&
+                    sizeof(ML::red) + sizeof(ML::hid) + sizeof(ML::obuf) >= sizeof(float) * MR * HD, "hidden rows in red .. obuf");
+      float* hall = &red[0][0][0];
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < EPH; i++) hall[tid + NT * i] = hv[i];
+      __syncthreads();
+      if (!ps_sweeps_ok(ps)) return false;
+      float o2[MR][4];
+#pragma unroll
+      for (int r = 0; r < MR; r++) { o2[r][0] = o2[r][1] = o2[r][2] = o2[r][3] = 0.f; }
+#pragma unroll
+      for (int r = 0; r < MR; r++) {
+        if ((deadm >> r) & 1) continue;
+#pragma unroll
+        for (int i4 = 0; i4 < RPG; i4 += 4) {
+          const float4 h4 = *reinterpret_cast<const float4*>(&hall[r * HD + ch2 * RPG + i4]);
+          const float hq[4] = {h4.x, h4.y, h4.z, h4.w};
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const float hvv = hq[i];
+            o2[r][0] += hvv * w2[i4 + i].x; o2[r][1] += hvv * w2[i4 + i].y; o2[r][2] += hvv * w2[i4 + i].z; o2[r][3] += hvv * w2[i4 + i].w;
+          }
+        }
+      }
+      // the row groups of a slice, g ascending (the order the planes' obuf pass used); the slice's sum lands in its g = 0 lanes
+      float* pbuf = &hs[0][0];                       // [MR][NB2][16]: exactly the rows' LDS copy, read for the last time above
+      const bool g0 = (tid >> 2) < NCH && ((tid >> 2) % G) == 0;
+      const int jsl = (tid >> 2) / G;
+#pragma unroll
+      for (int r = 0; r < MR; r++) {
+        if ((deadm >> r) & 1) continue;
+        float s4[4] = {o2[r][0], o2[r][1], o2[r][2], o2[r][3]};
+#pragma unroll
+        for (int g2 = 1; g2 < G; g2++)
+#pragma unroll
+          for (int k = 0; k < 4; k++) s4[k] += lane_get(o2[r][k], (lane + 4 * g2) & 63);
+        if (g0) *reinterpret_cast<float4*>(&pbuf[(r * NB2 + jsl) * CB + cq * 4]) = make_float4(s4[0], s4[1], s4[2], s4[3]);
+      }
+      __syncthreads();
+      if (tid < MR * CB) {
+        const int r = tid >> 4, c = tid & (CB - 1);
+        if (r < n_rows && !((deadm >> r) & 1)) {
+          float accp = b2v;
+#pragma unroll
+          for (int j = 0; j < NB2; j++) accp += pbuf[(r * NB2 + j) * CB + c];            // s ascending (mod.rs:346-348)
+          st_gran(Buf16(a.g_x_out), (uint32_t)(r * d + jblk * CB + c), ps.tag_out, xown + accp);
+        }
+      }
+      ps_stamp(ps, 5);
+      return true;
+    }
   }
   __syncthreads();
   WB_STAMP(3);
+  if constexpr (PS) ps_stamp(ps, 4);
   float o[MR][4];
 #pragma unroll
   for (int r = 0; r < MR; r++) { o[r][0] = o[r][1] = o[r][2] = o[r][3] = 0.f; }
@@ -725,6 +853,7 @@ __device__ __forceinline__ bool dec_mlp_body(const MlpFusedArgs& a, const int jb
       }
     }
   }
+  if constexpr (PS) ps_stamp(ps, 5);
   WB_STAMP(4);
   WB_STAMP_FLUSH(a, 5);
   return true;
@@ -883,7 +1012,7 @@ __device__ __forceinline__ bool dec_attn_body(const AttnFusedArgs& a, const int 
       const Buf16 xgb(a.g_x_in), pgb(a.g_pend);
       const uint32_t pvo = (uint32_t)(r * d + c);
       const int iplane = a.S * d;
-      if (a.KSp > 0) ps_nap<2>();                   // (the previous layer's MLP has only just started)
+      if (a.KSp > 0 || ps.x_late) ps_nap<2>();      // (the previous layer's MLP has only just started)
       constexpr int FP = 4 * DPL;                   // the 4 d / 64 planes of the previous layer's MLP
       float accp = a.KSp > 0 ? gld(a.pbias + c) : 0.f;
       unsigned sweeps = 0;
@@ -1355,7 +1484,11 @@ __device__ __forceinline__ bool dec_cross_body(const CrossFusedArgs& a, const in
       const uint32_t pvo = (uint32_t)(r * d + c);
       const int iplane = a.S * d;
       // (the self-attention blocks have only just started; behind a picking first-layer role they are well under way)
-      if (ps.cross_early) ps_nap<WB_PS_CROSS0_NAP>(); else ps_nap<4>();
+      // (x_late: two-phase MLP roles arrive ~1.5 us later relative to the self-attention roles they release, so 2.5 units
+      // (4.25 us) instead of 4: with 4 the sweep started 2 us after the planes had landed, profiles/r22_ps_timeline_tree_deal0.txt)
+      if (ps.cross_early) ps_nap<WB_PS_CROSS0_NAP>();
+      else if (ps.x_late) { ps_nap<2>(); __builtin_amdgcn_s_sleep(32); }
+      else ps_nap<4>();
       constexpr int FP = 8;                         // <= 8 head planes
       float v = 0.f, accp = gld(a.pbias + c);
       unsigned sweeps = 0;

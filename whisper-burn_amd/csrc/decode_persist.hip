@@ -12,8 +12,9 @@
 //
 // Roles of one step, in dependency order:
 //   per layer l: attn (head h, row r) x H R  ->  cross (h, r) x H R  ->  mlp (64-unit hidden slice j) x 4 d / 64
-//   final LN (row r) x R: ln(x + last MLP planes), once per row   ->   logits (a run of 128-column vocabulary tiles)
-//   ->   merge (row r) x R
+//   logits (a run of 128-column vocabulary tiles; each applies the final LayerNorm to the rows itself)   ->   merge (row r) x R
+//   (WHISPER_HIP_PERSIST_MLP=planes, and any grid with fewer than 4 d / 64 blocks: a final-LN role (row r) x R in front of the
+//   logits roles, ln(x + last MLP planes) once per row -- "the MLP edge" below)
 // The host deals the roles to the blocks (decode_chain.cpp): a block runs its own list, in dependency order, every step.  The
 // first sublayers' blocks take no logits work (they are back at their wait, weights requested, before the step ends).
 // Dependencies = arrival counters (handoff.h), monotonic within the launch:
@@ -21,14 +22,38 @@
 //                pre-wake on the GO word of epoch e and on c_x[r] >= e - 1.  Step 0, behind a prompt step, a row that ends,
 //                WHISPER_HIP_PERSIST_PICK=merge: waits for merge(r) of the previous step (its x row)   c_x[r] >= e
 //   cross(0,.,r) pre-wake: merge(r) of the previous step                       c_x[r]       >= e
-//   attn(l,.,r)  waits for every MLP slice of layer l - 1                      c_mlp[l-1]   >= (e + 1) NB
+//   attn(l,.,r)  pre-wake: the cross-attention blocks of layer l - 1; then the row's granules from the MLP roles of layer l - 1
 //   cross(l,.,r) waits for the H attention blocks of its row                   c_attn[l][r] >= (e + 1) H
 //   mlp(l,.)     waits for every cross-attention block of the layer            c_cross[l]   >= (e + 1) H R
-//   logits(.)    waits for every MLP slice of the last layer                   c_mlp[NL-1]  >= (e + 1) NB
+//   logits(.)    pre-wake: the last layer's cross-attention blocks (GO words); then the rows' granules from its MLP roles
 //   merge(r)     waits for every logits role (8 counters, role q arrives at q mod 8)  c_log[k] >= (e + 1) n_k
 // Every block's list follows one global dependency order and all blocks are co-resident (the host sizes the grid from
 // the occupancy query), so the smallest unfinished role can always run: no deadlock.  Reuse of the plane
 // buffers across steps is ordered by the same chain (a role arrives only after its last read).
+//
+// The MLP edge.  An MLP role is split over the hidden dimension for both matrices.  In the `planes` form block j leaves a full-
+// width partial of hid . W2 and every consumer block re-sums 4 d / 64 planes (77 KB swept per block at d = 384; a final-LN role per
+// row does it once for the logits blocks).  Default, two phases (decode_fused_bodies.h: dec_mlp_body): block j publishes its 64
+// hidden values per live row into g_hid [S][4 d] (tag = the role's tag_out), sweeps all 4 d of them -- no counter: the data is
+// the flag -- and finishes the 16 residual columns [16 j, 16 j + 16) with the same sums, operand for operand and in the same
+// order, that the planes and the consumers' folds went through; the columns go straight into the next stage's x stream as
+// granules with tag_out.  attn(l + 1) takes the row as a finished stream (KSp = 0, the path layer 0 always used) and the logits
+// roles sweep the last layer's rows and normalise them per wave (ps_finln_role's expression on the same operands): no planes, no
+// plane bias on that edge, no stream store by slice 0, no final-LN stage.  The role arrives on c_mlp[l] behind phase 2.
+//   * g_hid is ONE buffer for all layers and steps.  Its readers are the phase-2 sweeps of the stage that wrote it.  The next
+//     writer is phase 1 of the next MLP stage (layer l + 1, or layer 0 of step e + 1); that stage runs behind cross(l + 1) <-
+//     attn(l + 1) <- the finished row of a live row, which exists only when ALL 4 d / 64 blocks of stage l have published their
+//     columns, i.e. behind their sweeps (a block publishes after its whole sweep, and a sweep's loads have returned when its
+//     values are used).  Across the step boundary the same chain runs through logits -> records / merge -> attn(0).  No new
+//     counter and no new tag value: a stale granule of g_hid carries another stage's tag.
+//   * The x stream buffer the columns go to was last read by cross(l) (its attention stream); the MLP role has folded those
+//     roles' planes before phase 1, so their reads are over -- the order slice 0's stream store relied on.
+//   * Phase 2 waits for roles of the SAME stage, so the 4 d / 64 MLP roles of a layer must sit on different blocks ("the
+//     smallest unfinished role can always run" would not hold otherwise): the host selects this form only on a grid of at least
+//     4 d / 64 blocks (layer role i sits on block i % grid) and the `planes` form below that (decode_chain.cpp).
+//   * x_fin, the rows the logits roles sweep, is overwritten by merge(r) of the same step (even layer counts: it is x0) -- behind
+//     every logits arrival -- or by attn(0) of the next step (odd layer counts), which has seen every tile record of the row
+//     or waited for merge(r); either way behind the logits roles' sweeps.  The final-LN role's read of x_fin was ordered the same way.
 //
 // The step boundary.  The logits roles leave one 16-byte record {tag, value, tag, id} per (row, tile), tagged with the step's
 // final-LN tag, in the buffer of the step's parity.  attn(0,h,r) of step e sweeps row r's records of step e - 1, takes the argmax
@@ -125,12 +150,14 @@ __device__ __forceinline__ bool ps_finln_role(const PersistArgs& a, const int r,
 }
 
 // ---- logits role: tiles of  xn . E^T  (mod.rs:156), last position only ----------------------------------------------------
-// Both E^T tiles of the role (d x 128 floats = d / 16 float4 per thread each) are in flight before the wait.  The normalised
-// rows arrive as granules from the final-LN roles.  Per row and tile the block leaves the best masked logit and its id --
+// Both E^T tiles of the role (d x 128 floats = d / 16 float4 per thread each) are in flight before the wait.  The
+// rows arrive as granules: finished rows of the last layer's MLP roles, normalised here (a.mlp2), or rows already normalised
+// by the final-LN roles (planes form).  Per row and tile the block leaves the best masked logit and its id --
 // greedy needs the argmax only (log_softmax is monotone: transcribe.rs:276 with beam.rs k = 1).
 template <int MR, int DPL>
 struct LogitsLds {
   alignas(16) float xs[MR][64 * DPL];
+  alignas(16) float xn[MR][64 * DPL];              // (final LayerNorm inside the role: every wave's own k-range of ln(xs))
   alignas(16) float red[8][MR][PS_CT];
   float tilev[MR][PS_CT];
 };
@@ -146,6 +173,13 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
   auto& xs = sm.xs; auto& red = sm.red; auto& tilev = sm.tilev;
   const int tid = role_tid<true>(), lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, c4 = (lane & 31) * 4;
+  // a.mlp2: the rows arrive finished but not normalised (the last layer's MLP roles' columns); every wave takes the rows'
+  // statistics itself and normalises the 2 NR columns its own E^T rows multiply -- ps_finln_role's expression on the same
+  // operands, no barrier beyond the one behind the sweep.  Lane l < 2 NR owns column 2 wave NR + l
+  const bool own_ln = a.mlp2 != 0;
+  const int ln_col = 2 * wave * NR + (lane < 2 * NR ? lane : 0);
+  float g_own = 0.f, b_own = 0.f;
+  if (own_ln) { g_own = gld(a.ln_g + ln_col); b_own = gld(a.ln_b + ln_col); }
   // (buffer loads: one lane offset, the row offset i vocab_ld rides in the scalar offset -- 24 64-bit addresses per lane
   // would otherwise live across the tile loop)
   const Buf16 etb(a.Et);
@@ -171,7 +205,8 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
   if (!ps_wait(ps)) return false;                   // pre-wake: the last layer's cross-attention blocks have finished
   // (no nap: the wake-up word reaches a few hundred pollers ~9 us after the broadcast -- the last MLP has finished by then)
   {
-    // the normalised rows: MR d granules, re-read until every live row carries the final-LN roles' tag
+    // the rows (a.mlp2: finished, not yet normalised; else the final-LN roles' normalised ones): MR d granules, re-read until
+    // every live row carries the producing stage's tag
     int off[EPT];
 #pragma unroll
     for (int i = 0; i < EPT; i++) {
@@ -182,7 +217,7 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
 #pragma unroll
     for (int r = 0; r < MR; r++)
       if (r >= ps.n_rows || ld_i<true>(ps.dead + min(r, ps.n_rows - 1)) != 0) deadm |= 1 << r;
-    const Buf16 xgb(a.g_xn);
+    const Buf16 xgb(own_ln ? a.x_fin : a.g_xn);
     float v[EPT];
     unsigned sweeps = 0;
     for (;;) {
@@ -209,9 +244,23 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
   __syncthreads();
   if (!ps_sweeps_ok(ps)) return false;
   ps_stamp(ps, 3);
-  // a prompt step: the role has kept its place in the chain (it arrives after the final-LN roles, the merge role after it --
+  // a prompt step: the role has kept its place in the chain (it arrives after the rows' producers, the merge role after it --
   // the order the reuse of the x rows and planes relies on) and is done
   if (forced) return true;
+  const float (*xg)[d] = xs;                        // what the GEMV multiplies
+#if !defined(WB_PS_DRY)
+  if (own_ln) {
+#pragma unroll
+    for (int r = 0; r < MR; r++) {
+      if ((deadm >> r) & 1) continue;
+      float mean, denom;
+      ln_stats_lds<DPL>(xs[r], d, lane, a.ln_eps, a.ln_inside, mean, denom);
+      if (lane < 2 * NR) sm.xn[r][ln_col] = (xs[r][ln_col] - mean) / denom * g_own + b_own;
+    }
+    __builtin_amdgcn_wave_barrier();                // (a wave reads back only the columns its own lanes wrote)
+    xg = sm.xn;
+  }
+#endif
 #if defined(WB_PS_DRY)
   // dry build (tools/build_exp.sh dry): the role's tile records without the E^T stream and the GEMV -- token 0-ish every step
   for (int t = 0; t < n_t; t++)
@@ -238,7 +287,7 @@ __device__ __forceinline__ bool ps_logits_role(const PersistArgs& a, const int t
       if ((deadm >> r) & 1) continue;               // (rows whose window has ended cost nothing)
 #pragma unroll
       for (int i4 = 0; i4 < NR; i4 += 4) {
-        const float4 xv = *reinterpret_cast<const float4*>(&xs[r][(2 * wave + hh) * NR + i4]);
+        const float4 xv = *reinterpret_cast<const float4*>(&xg[r][(2 * wave + hh) * NR + i4]);
         acc[r][0] += xv.x * w[i4].x; acc[r][1] += xv.x * w[i4].y; acc[r][2] += xv.x * w[i4].z; acc[r][3] += xv.x * w[i4].w;
         acc[r][0] += xv.y * w[i4 + 1].x; acc[r][1] += xv.y * w[i4 + 1].y; acc[r][2] += xv.y * w[i4 + 1].z; acc[r][3] += xv.y * w[i4 + 1].w;
         acc[r][0] += xv.z * w[i4 + 2].x; acc[r][1] += xv.z * w[i4 + 2].y; acc[r][2] += xv.z * w[i4 + 2].z; acc[r][3] += xv.z * w[i4 + 2].w;
@@ -447,7 +496,8 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
       // step e - 1 chose its token (it was no prompt step) and this step's position row exists: the pick edge
       const bool pick_e = a.pick != 0 && e >= 1 && e - 1 >= a.n_forced && ps.step < a.Lmax;
       if (role.kind == PSR_ATTN) {
-        const AttnFusedArgs la = a.layers[role.layer].attn;
+        AttnFusedArgs la = a.layers[role.layer].attn;
+        if (a.mlp2) { la.KSp = 0; ps.x_late = role.layer > 0; }   // (the previous layer's MLP roles left the finished row: nothing to fold)
         // layer 0: the merge role's flag (its x row follows as granules); else pre-wake = the previous layer's
         // cross-attention blocks have finished (its MLP, the producer, is running)
         if (role.layer == 0) { ps.ctr_index = C_X + role.b; ps.target = (unsigned)e; }
@@ -471,6 +521,7 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_out = tag_l + 1u; ps.tag_in = tag_l;
         ps.cross_early = role.layer == 0 && pick_e;
+        ps.x_late = a.mlp2 != 0 && role.layer > 0;   // (its pre-wake, the previous layer's MLP roles' arrival, comes later)
         ok = dec_cross_body<DPL, true, NP, RS>(la, role.a, role.b, ps, lds.cross, i == res_i ? res_buf : nullptr);
         out = C_CROSS + role.layer;
       } else if (role.kind == PSR_MLP) {
@@ -479,6 +530,10 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         ps.ctr_index = C_ATTN + role.layer * S; ps.target = (unsigned)(e + 1) * H; ps.n_ctr = R;
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_out = tag_l + 2u; ps.tag_in = tag_l + 1u;
+        if (a.mlp2) {
+          ps.mlp_hid = a.g_hid;
+          ps.mlp_b2 = a.layers[role.layer].mlp_b2;
+        }
         ok = dec_mlp_body<MR, DPL, false, true>(la, role.a, ps, lds.mlp);
         out = C_MLP + role.layer;
       } else if (role.kind == PSR_FINLN) {
@@ -489,8 +544,8 @@ __global__ __launch_bounds__(PS_NT) void dec_persist_kernel(PersistArgs a) {
         out = C_GO + PS_NGO;                         // (nobody waits for it: the logits roles watch the granules)
       } else if (role.kind == PSR_LOGITS) {
         // a few hundred blocks: pre-woken by the last cross-attention block of the step through one of PS_NGO words; they
-        // nap, then watch the final-LN roles' d granules per row (a sweep of all 4 d / 64 MLP planes by every logits block
-        // was 22 MB per round: profiles/r03_c_ps_timeline_granules_v1.txt)
+        // nap, then watch d granules per row -- the last layer's finished rows, or the final-LN roles' (a sweep of all 4 d / 64
+        // MLP planes by every logits block was 22 MB per round: profiles/r03_c_ps_timeline_granules_v1.txt)
         ps.ctr_index = C_GO + (role.layer % PS_NGO); ps.target = (unsigned)(e + 1);
         ps.ctr = cptr(ps.ctr_index);
         ps.tag_in = tag_l + 2u;
@@ -530,6 +585,45 @@ __global__ __launch_bounds__(PS_NT) void ps_pick_test_kernel(const void* rec, in
   __syncthreads();
   const int tok = ps_pick_token(rec, n_tiles, tag, ps, xch, role_tid<true>());
   if (threadIdx.x == 0) *out_id = ps_sweeps_ok(ps) ? tok : -1;
+}
+
+// test-only (tools/kernel_harness.cpp: wbk_persist_mlp2): the MLP roles of one layer in the two-phase form, block j = slice j
+template <int DPL>
+__global__ __launch_bounds__(PS_NT) void ps_mlp2_test_kernel(PsMlp2TestArgs t) {
+  __shared__ MlpLds<4, DPL, false> sm;
+  __shared__ int flag;
+  PsStep ps;
+  ps.ctl = t.ctl; ps.step = -1; ps.lds_flag = &flag;   // (step -1: the zeroed stop word stops nothing)
+  ps.ctr = reinterpret_cast<const unsigned*>(t.ctl + HX_HDR); ps.target = 0u;   // (the wait is passed at once)
+  ps.n_rows = t.n_rows; ps.dead = t.dead;
+  ps.tag_in = t.tag_in; ps.tag_out = t.tag_in + 1u;
+  ps.mlp_hid = t.g_hid; ps.mlp_b2 = t.b2;
+  dec_mlp_body<4, DPL, false, true>(t.a, blockIdx.x, ps, sm);
+}
+
+// test-only (tools/kernel_harness.cpp: wbk_persist_logits): one logits role, behind the final-LN roles of its rows in the planes form
+template <int DPL>
+struct PsLogitsTestLds { union { FinLnLds<DPL> finln; LogitsLds<4, DPL> logits; }; };
+struct PsLogitsTestArgs { PersistArgs a; unsigned tag; int n_t; };
+template <int DPL>
+__global__ __launch_bounds__(PS_NT) void ps_logits_test_kernel(PsLogitsTestArgs t) {
+  const PersistArgs& a = t.a;
+  const unsigned tag = t.tag;
+  const int n_t = t.n_t;
+  __shared__ PsLogitsTestLds<DPL> sm;
+  __shared__ int flag;
+  PsStep ps;
+  ps.ctl = a.ctl; ps.step = -1; ps.lds_flag = &flag;   // (step -1: the zeroed stop word stops nothing; a.mask_until_len < 0: no mask)
+  ps.ctr = reinterpret_cast<const unsigned*>(a.ctl + HX_HDR); ps.target = 0u;   // (every wait is passed at once)
+  ps.n_rows = a.n_rows; ps.dead = a.dead;
+  ps.tag_in = tag; ps.tag_out = tag;
+  if (blockIdx.x == 0) {                             // block 0: the rows' final-LN roles (planes form); block 1: the logits role
+    if (a.mlp2 == 0)
+      for (int r = 0; r < a.n_rows; r++)
+        if (!ps_finln_role<DPL>(a, r, ps, sm.finln)) return;
+    return;
+  }
+  ps_logits_role<4, DPL>(a, 0, n_t, ps, false, 0, sm.logits);
 }
 
 template <int DPL, int MR, int NP>
@@ -604,6 +698,24 @@ void launch_ps_seed(hipStream_t st, const float* x, int n, void* gx, unsigned ta
 
 void launch_ps_pick_test(hipStream_t st, const void* rec, int n_tiles, unsigned tag, int* ctl, int* out_id) {
   hipLaunchKernelGGL(ps_pick_test_kernel, dim3(1), dim3(PS_NT), 0, st, rec, n_tiles, tag, ctl, out_id);
+}
+
+int launch_ps_mlp2_test(hipStream_t st, const PsMlp2TestArgs& t) {
+  if ((t.a.d != 128 && t.a.d != 384) || t.n_rows < 1 || t.n_rows > 4 || t.n_rows > t.a.S) return -1;
+  const dim3 g(4 * t.a.d / 64), b(PS_NT);
+  hipError_t e;
+  if (t.a.d == 128) e = WB_LAUNCH_COOP((ps_mlp2_test_kernel<2>), g, b, 0, st, t);
+  else e = WB_LAUNCH_COOP((ps_mlp2_test_kernel<6>), g, b, 0, st, t);
+  return e == hipSuccess ? 0 : -1;
+}
+
+int launch_ps_logits_test(hipStream_t st, const PersistArgs& a, unsigned tag, int n_t) {
+  if ((a.d != 128 && a.d != 384) || a.n_rows < 1 || a.n_rows > 4 || a.n_rows > a.S || n_t < 1 || n_t > 2 || n_t > a.n_tiles) return -1;
+  // (a cooperative launch like the kernel it stands for: the roles nap and re-read, which the functional model allows only there)
+  const PsLogitsTestArgs t{a, tag, n_t};
+  const dim3 g(2), b(PS_NT);
+  const hipError_t e = a.d == 128 ? WB_LAUNCH_COOP((ps_logits_test_kernel<2>), g, b, 0, st, t) : WB_LAUNCH_COOP((ps_logits_test_kernel<6>), g, b, 0, st, t);
+  return e == hipSuccess ? 0 : -1;
 }
 
 int launch_dec_persist(hipStream_t st, const PersistArgs& a, int grid) {

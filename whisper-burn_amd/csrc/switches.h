@@ -58,6 +58,7 @@ enum Kind { DEFAULT_ON, OPT_IN, UNSET_OR_1, TRI, INT, STR };
   X(persist_setup, "WHISPER_HIP_PERSIST_SETUP", STR, nullptr, "persistent kernel: launch setup cached on the session (on); 0: built per call; log: on + report; 0log: both") \
   X(persist_deal, "WHISPER_HIP_PERSIST_DEAL", STR, nullptr, "persistent kernel: merge / final-LN roles kept off the first-layer attention blocks (on); legacy: the least loaded blocks; log: on + report") \
   X(persist_pick, "WHISPER_HIP_PERSIST_PICK", STR, nullptr, "persistent kernel: first-layer self-attention picks the next token from the tile records itself (on); merge: it waits for the merge role's row") \
+  X(persist_mlp, "WHISPER_HIP_PERSIST_MLP", STR, nullptr, "persistent kernel: the MLP role publishes finished residual columns and the logits roles apply the final LayerNorm (on); planes: 4 d / 64 partial planes per layer and a final-LN role") \
   X(persist_inject_fail, "WHISPER_HIP_PERSIST_INJECT_FAIL", STR, nullptr, "test hook: \"launch\" = the cooperative launch is refused")
 
 #define WB_SW_DECL(fn, name, kind, dflt, what) bool fn();

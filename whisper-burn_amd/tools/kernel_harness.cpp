@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -558,6 +559,114 @@ int wbk_persist_pick(WbkPick* t) {
   int id = -1;
   P.ok(hipMemcpy(&id, dout, 4, hipMemcpyDeviceToHost));
   t->out_id = id;
+  return P.err;
+}
+
+// launch_ps_mlp2_test (decode_persist.hip) next to launch_dec_mlp_fused (decode_fused.hip) on the same inputs: one layer's MLP
+// over n_rows <= 4 rows (S = n_rows).  x_in [S][d], pend [KSp][S][d] (the cross-attention planes), pbias [d], W1 [d][ld1], b1 [4 d],
+// W2 [4 d][d], b2 [d], dead [S] int32 (two-phase form only: != 0 masks the row).  Out: rows2 [S][d] + tags2 [S][d] (uint32) = the
+// two-phase roles' finished rows and their granule tags (tag_out = tag_in + 1 where a row was written, 0 elsewhere); P
+// [4 d / 64][S][d] and x_out [S][d] = what the one-launch kernel leaves (the consumer folds x_out + (b2 + sum_j P[j])).
+struct WbkMlp2 {
+  WbkBuf x_in, pend, pbias, ln_g, ln_b, W1, b1, W2, b2, dead, rows2, tags2, P, x_out;
+  int64_t S, d, KSp, ld1, ln_inside, tag_in;
+  double ln_eps;
+};
+
+int wbk_persist_mlp2(WbkMlp2* t) {
+  const int64_t S = t->S, d = t->d, K = t->KSp, NB = 4 * d / 64;
+  if ((d != 128 && d != 384) || S < 1 || S > 4 || K < 1 || K > 8 || t->ld1 < 4 * d || t->ld1 % 4) return WBK_EARG;
+  if (t->tag_in < 1 || t->tag_in > 0xfffffff0ll) return WBK_EARG;
+  if (!inside(t->x_in, 0, S * d, 4) || !inside(t->pend, 0, K * S * d, 4) || !inside(t->pbias, 0, d, 4)) return WBK_EARG;
+  if (!inside(t->ln_g, 0, d, 4) || !inside(t->ln_b, 0, d, 4) || !inside(t->b1, 0, 4 * d, 4) || !inside(t->b2, 0, d, 4)) return WBK_EARG;
+  if (!inside(t->W1, 0, (d - 1) * t->ld1 + 4 * d, 4) || !aligned16(t->W1, 0, 4) || !inside(t->W2, 0, 4 * d * d, 4) || !aligned16(t->W2, 0, 4)) return WBK_EARG;
+  if (!inside(t->dead, 0, S, 4) || !inside(t->rows2, 0, S * d, 4) || !inside(t->tags2, 0, S * d, 4)) return WBK_EARG;
+  if (!inside(t->P, 0, NB * S * d, 4) || !aligned16(t->P, 0, 4) || !inside(t->x_out, 0, S * d, 4)) return WBK_EARG;
+  // the role's inputs as {tag, value} granules
+  auto granules = [&](const WbkBuf& b, int64_t n) {
+    std::vector<uint32_t> g((size_t)n * 2);
+    const uint32_t* v = (const uint32_t*)((const char*)b.host + b.off);
+    for (int64_t i = 0; i < n; i++) { g[2 * i] = (uint32_t)t->tag_in; g[2 * i + 1] = v[i]; }
+    return g;
+  };
+  std::vector<uint32_t> gx = granules(t->x_in, S * d), gp = granules(t->pend, K * S * d);
+  std::vector<uint32_t> gout((size_t)(S + 8) * d * 2, 0u), ghid((size_t)(S + 2) * 4 * d * 2, 0u);
+  std::vector<int32_t> ctl((size_t)wb::ps_ctl_ints(1, 1), 0);
+  const wb::StepLayout lay = wb::make_step_layout((int)S, 1);
+  std::vector<int32_t> st((size_t)lay.total, 0);
+  st[wb::ST_N] = (int32_t)S;
+  auto vb = [](auto& v) { return WbkBuf{v.data(), (int64_t)(v.size() * sizeof(v[0])), 0}; };
+  const WbkBuf gxb = vb(gx), gpb = vb(gp), goutb = vb(gout), ghidb = vb(ghid), ctlb = vb(ctl), stb = vb(st);
+
+  Pool P;
+  char *dx = upload(P, t->x_in), *dpe = upload(P, t->pend), *dpb = upload(P, t->pbias), *dg = upload(P, t->ln_g), *db = upload(P, t->ln_b);
+  char *dW1 = upload(P, t->W1), *db1 = upload(P, t->b1), *dW2 = upload(P, t->W2), *db2 = upload(P, t->b2), *ddead = upload(P, t->dead);
+  char *dP = upload(P, t->P), *dxo = upload(P, t->x_out);
+  char *dgx = upload(P, gxb), *dgp = upload(P, gpb), *dgo = upload(P, goutb), *dgh = upload(P, ghidb), *dctl = upload(P, ctlb), *dst = upload(P, stb);
+  if (P.err) return P.err;
+  auto at = [](char* p, const WbkBuf& b) -> char* { return p ? p + b.off : nullptr; };
+  wb::MlpFusedArgs a;
+  a.st = (const int*)dst; a.S = (int)S; a.d = (int)d;
+  a.x_in = (const float*)at(dx, t->x_in); a.pend = (const float*)at(dpe, t->pend); a.KSp = (int)K; a.pbias = (const float*)at(dpb, t->pbias);
+  a.x_out = (float*)at(dxo, t->x_out);
+  a.ln_g = (const float*)at(dg, t->ln_g); a.ln_b = (const float*)at(db, t->ln_b); a.ln_eps = (float)t->ln_eps; a.ln_inside = (int)t->ln_inside;
+  a.W1 = (const float*)at(dW1, t->W1); a.ld1 = (int)t->ld1; a.b1 = (const float*)at(db1, t->b1); a.W2 = (const float*)at(dW2, t->W2);
+  a.P = (float*)at(dP, t->P);
+  a.g_x_in = dgx; a.g_pend = dgp; a.g_x_out = dgo; a.g_P = nullptr;
+  wb::launch_dec_mlp_fused(nullptr, a, (int)S);
+  int status = finish(P, 0);
+  if (status) return status;
+  wb::PsMlp2TestArgs ta;
+  ta.a = a; ta.n_rows = (int)S; ta.dead = (const int*)at(ddead, t->dead); ta.g_hid = dgh; ta.b2 = (const float*)at(db2, t->b2);
+  ta.tag_in = (unsigned)t->tag_in; ta.ctl = (int*)dctl;
+  status = finish(P, wb::launch_ps_mlp2_test(nullptr, ta));
+  if (status) return status;
+  download(P, t->P, dP); download(P, t->x_out, dxo); download(P, goutb, dgo);
+  uint32_t* r2 = (uint32_t*)((char*)t->rows2.host + t->rows2.off); uint32_t* t2 = (uint32_t*)((char*)t->tags2.host + t->tags2.off);
+  for (int64_t i = 0; i < S * d; i++) { t2[i] = gout[2 * i]; r2[i] = gout[2 * i + 1]; }
+  return P.err;
+}
+
+// launch_ps_logits_test (decode_persist.hip): ONE logits role of the persistent kernel over tiles 0 .. n_t - 1 and n_rows <= 4 rows
+// (S = n_rows).  x [S][d]: the last layer's finished rows; ln_g / ln_b [d]; Et [d][vocab_ld] (vocab_ld % 4 == 0, >= 128 n_t);
+// dead [S] int32.  mlp2 = 1: the role takes the rows as granules and normalises them itself.  mlp2 = 0: the final-LN role of every
+// row runs first (no planes to fold, a zero bias: it leaves ln(x + 0)), then the logits role on its rows.  rec: [S][n_t] records of
+// 16 bytes {tag, value, tag, id}, zero where nothing was stored.
+struct WbkLogits {
+  WbkBuf x, ln_g, ln_b, Et, dead, rec;
+  int64_t S, d, V, vocab_ld, n_t, ln_inside, tag, mlp2;
+  double ln_eps;
+};
+
+int wbk_persist_logits(WbkLogits* t) {
+  const int64_t S = t->S, d = t->d, nt = t->n_t, ld = t->vocab_ld;
+  if ((d != 128 && d != 384) || S < 1 || S > 4 || nt < 1 || nt > 2 || ld % 4 || ld < 128 * nt || t->V < 1 || t->V > ld) return WBK_EARG;
+  if ((t->V + 127) / 128 != nt || t->tag < 1 || t->tag > 0xfffffff0ll || (t->mlp2 != 0 && t->mlp2 != 1)) return WBK_EARG;
+  if (!inside(t->x, 0, S * d, 4) || !inside(t->ln_g, 0, d, 4) || !inside(t->ln_b, 0, d, 4) || !inside(t->dead, 0, S, 4)) return WBK_EARG;
+  if (!inside(t->Et, 0, d * ld, 4) || !aligned16(t->Et, 0, 4) || !inside(t->rec, 0, S * nt * 4, 4) || !aligned16(t->rec, 0, 4)) return WBK_EARG;
+  std::vector<uint32_t> gx((size_t)(S + 8) * d * 2, 0u), gxn((size_t)(S + 8) * d * 2, 0u);
+  const uint32_t* xv = (const uint32_t*)((const char*)t->x.host + t->x.off);
+  for (int64_t i = 0; i < S * d; i++) { gx[2 * i] = (uint32_t)t->tag; gx[2 * i + 1] = xv[i]; }
+  std::vector<float> zero((size_t)d, 0.f);
+  std::vector<uint32_t> rec((size_t)S * nt * 4, 0u);
+  std::vector<int32_t> ctl((size_t)wb::ps_ctl_ints(1, 1), 0);
+  auto vb = [](auto& v) { return WbkBuf{v.data(), (int64_t)(v.size() * sizeof(v[0])), 0}; };
+  const WbkBuf gxb = vb(gx), gxnb = vb(gxn), zb = vb(zero), recb = vb(rec), ctlb = vb(ctl);
+  Pool P;
+  char *dg = upload(P, t->ln_g), *db = upload(P, t->ln_b), *dE = upload(P, t->Et), *ddead = upload(P, t->dead);
+  char *dgx = upload(P, gxb), *dgxn = upload(P, gxnb), *dz = upload(P, zb), *drec = upload(P, recb), *dctl = upload(P, ctlb);
+  if (P.err) return P.err;
+  auto at = [](char* p, const WbkBuf& b) -> char* { return p ? p + b.off : nullptr; };
+  wb::PersistArgs a;
+  a.n_rows = (int)S; a.S = (int)S; a.d = (int)d; a.nb_mlp = 0; a.ctl = (int*)dctl; a.mask_until_len = -4;
+  a.x_fin = dgx; a.P2 = dgx; a.b2_last = (const float*)dz; a.g_xn = dgxn;
+  a.ln_g = (const float*)at(dg, t->ln_g); a.ln_b = (const float*)at(db, t->ln_b); a.ln_eps = (float)t->ln_eps; a.ln_inside = (int)t->ln_inside;
+  a.Et = (const float*)at(dE, t->Et); a.vocab_ld = (int)ld; a.V = (int)t->V; a.mask = nullptr;
+  a.tstats = drec; a.n_tiles = (int)nt; a.mlp2 = (int)t->mlp2; a.dead = (int*)at(ddead, t->dead);
+  const int status = finish(P, wb::launch_ps_logits_test(nullptr, a, (unsigned)t->tag, (int)nt));
+  if (status) return status;
+  download(P, recb, drec);
+  memcpy((char*)t->rec.host + t->rec.off, rec.data(), rec.size() * 4);
   return P.err;
 }
 
