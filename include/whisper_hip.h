@@ -114,7 +114,9 @@ int wb_model_set_frame_limit(wb_model* m, int whisper_geometry);
  *                              angle table b[k][n] = f32(f32(k) * f32(2 pi / 400)) * f32(n) on exact-f32 MFMA, the
  *                              log10 as ln(x) / f32(ln 10) and the clamp as relu(x - m8) + m8 on every element
  *                              (audio.rs:34-56, helper.rs:8-27): what the reference computes, to ~1e-5 on every bin.
- * Any other value -> WB_ERR_ARG (the mode is unchanged).  A session takes the mode at wb_session_begin. */
+ * Any other value -> WB_ERR_ARG (the mode is unchanged).  A session takes the mode at wb_session_begin.
+ * The reference recipe exists for 80 mel rows only (audio.rs:7): mode 1 on a 128-bin model (large-v3 and later) ->
+ * WB_ERR_ARG, the mode is unchanged. */
 enum { WB_FRONTEND_FFT = 0, WB_FRONTEND_REFERENCE = 1 };
 int wb_model_set_frontend(wb_model* m, int frontend);
 /* The current mode (0 / 1), WB_ERR_ARG for a null model. */
@@ -151,6 +153,11 @@ int wb_prep_audio(int device, const float* pcm, int64_t n, double sample_rate, f
  * wb_model_set_frontend); any other value -> WB_ERR_ARG. */
 int wb_prep_audio_frontend(int device, const float* pcm, int64_t n, double sample_rate, float* mel,
                            int64_t* n_frames, int frontend);
+/* wb_prep_audio with the number of mel rows chosen per call: n_mels = 80 (= wb_prep_audio, bit for bit) or 128 (the
+ * frontend of large-v3 and later: a filterbank designed in f64, see wb_mel_filterbank) -> [1,n_mels,n/160]; mel must hold
+ * n_mels*(n/160) floats.  K1 (WB_FRONTEND_FFT) always.  Any other n_mels -> WB_ERR_ARG. */
+int wb_prep_audio_mels(int device, const float* pcm, int64_t n, double sample_rate, int n_mels, float* mel,
+                       int64_t* n_frames);
 
 /* ---- WAV ingest with the reference's sample scaling (next to the hot path) ---------- */
 
@@ -199,8 +206,15 @@ int wb_waveform_to_mels_dev_frontend(int device, const float* pcm_dev, int64_t n
                                      const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
                                      int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
                                      int32_t* frames_out, int32_t iters, double* elapsed_ms, int32_t frontend);
+/* The same with the number of mel rows chosen per call as well: window w is written as [n_mels][row_stride]
+ * (win_stride >= n_mels * row_stride).  n_mels = 80 is wb_waveform_to_mels_dev_frontend bit for bit; n_mels = 128 (large-v3
+ * and later) has K1 only: WB_FRONTEND_REFERENCE there, or any other n_mels -> WB_ERR_ARG. */
+int wb_waveform_to_mels_dev_mels(int device, const float* pcm_dev, int64_t n_samples, double sample_rate,
+                                 const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
+                                 int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
+                                 int32_t* frames_out, int32_t iters, double* elapsed_ms, int32_t n_mels, int32_t frontend);
 
-/* Whisper::forward_encoder(mel [B,80,T]) -> [B,C,d], C=(T-1)/2+1, src/model/mod.rs:52-54,
+/* Whisper::forward_encoder(mel [B,n_mels,T]; n_mels = the model's, 80 or 128) -> [B,C,d], C=(T-1)/2+1, src/model/mod.rs:52-54,
  * :228-260.  T > n_audio_ctx -> WB_ERR_SHAPE (mod.rs:236-241). */
 int wb_forward_encoder(wb_model* m, const float* mel, int B, int T, float* out);
 
@@ -210,7 +224,7 @@ int wb_forward_encoder(wb_model* m, const float* mel, int B, int T, float* out);
 int wb_forward_decoder(wb_model* m, const int32_t* tokens, int n, int L, const float* enc, int C,
                        float* logits);
 
-/* Whisper::forward(mel [B,80,T], tokens [B,L]) -> logits [B,L,V], src/model/mod.rs:48-50 */
+/* Whisper::forward(mel [B,n_mels,T], tokens [B,L]) -> logits [B,L,V], src/model/mod.rs:48-50 */
 int wb_forward(wb_model* m, const float* mel, int B, int T, const int32_t* tokens, int L,
                float* logits);
 
@@ -239,7 +253,7 @@ void wb_decode_params_default(wb_decode_params* p);
 int wb_session_begin(wb_model* m, const float* pcm, int64_t n_pcm, const int64_t* starts,
                      const int64_t* lens, int n_windows, int max_beams, int padding,
                      wb_session** out);
-/* Same, from already-prepared mel windows mel[i] = [80, T[i]] packed back to back. */
+/* Same, from already-prepared mel windows mel[i] = [n_mels, T[i]] (n_mels = the model's) packed back to back. */
 int wb_session_begin_mel(wb_model* m, const float* mel, const int32_t* T, int n_windows,
                          int max_beams, int padding, wb_session** out);
 
@@ -796,6 +810,13 @@ int wb_find_repeated_tokens_index(const int32_t* tokens, int64_t n, int64_t wind
  * (hann_window_device, audio.rs:272-278) and the dense [80][201] Slaney filterbank (get_mel_filters_device,
  * audio.rs:67-143; the kernel keeps it sparse).  No GPU needed; for table-vs-oracle tests. */
 int wb_mel_constants(double sample_rate, float* hann400, float* filters_80x201);
+
+/* The dense [n_mels][201] filterbank of the frontend instance for n_mels rows, as its kernel uses it (host only).
+ * n_mels = 80: the table of wb_mel_constants, bit for bit.  n_mels = 128 (large-v3 and later): the Slaney bank designed in
+ * f64 as librosa evaluates it and rounded once to f32 -- the reference has no 128-row recipe, and its f32 op order loses
+ * too much on the narrow low rows.  Any other n_mels -> WB_ERR_ARG; a sample rate whose rows outgrow the kernel's tap
+ * capacity (16 per row at 80 rows, 12 at 128) -> WB_ERR_SHAPE. */
+int wb_mel_filterbank(double sample_rate, int n_mels, float* filters);
 
 /* The dense DFT table of the reference-recipe frontend (WB_FRONTEND_REFERENCE), built on the host as the kernel uses it
  * (before its padding to 416 rows): [402][400], row 2k = cos(b[k][n]) * w[n], row 2k+1 = sin(b[k][n]) * (-w[n]) for

@@ -130,6 +130,15 @@ extern "C" {
                          n_frames: *mut i64) -> c_int;
     pub fn wb_prep_audio_frontend(device: c_int, pcm: *const c_float, n: i64, sample_rate: c_double, mel: *mut c_float,
                                   n_frames: *mut i64, frontend: c_int) -> c_int;
+    // the number of mel rows chosen per call: 80, or 128 (large-v3 and later; K1 only)
+    pub fn wb_prep_audio_mels(device: c_int, pcm: *const c_float, n: i64, sample_rate: c_double, n_mels: c_int,
+                              mel: *mut c_float, n_frames: *mut i64) -> c_int;
+    pub fn wb_waveform_to_mels_dev_mels(device: c_int, pcm_dev: *const c_float, n_samples: i64, sample_rate: c_double,
+                                        starts: *const i64, lens: *const i64, n_windows: i32, clip_frames: i32,
+                                        padding: i32, mel_dev: *mut c_float, win_stride: i64, row_stride: i32,
+                                        frames_out: *mut i32, iters: i32, elapsed_ms: *mut c_double, n_mels: i32,
+                                        frontend: i32) -> c_int;
+    pub fn wb_mel_filterbank(sample_rate: c_double, n_mels: c_int, filters: *mut c_float) -> c_int;
     pub fn wb_mel_dft_table(table_402x400: *mut c_float) -> c_int;
     pub fn wb_forward_encoder(m: *mut wb_model, mel: *const c_float, b: c_int, t: c_int, out: *mut c_float) -> c_int;
     pub fn wb_forward_decoder(m: *mut wb_model, tokens: *const i32, n: c_int, l: c_int, enc: *const c_float, c: c_int,

@@ -113,6 +113,8 @@ int wb_model_set_frontend(wb_model* m, int frontend) {
   WB_REQUIRE(m, WB_ERR_ARG, "wb_model_set_frontend: null model");
   WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
              "wb_model_set_frontend: frontend %d is neither 0 (FFT) nor 1 (reference recipe)", frontend);
+  WB_REQUIRE(frontend == WB_FRONTEND_FFT || m->dims.n_mels == MEL_N_MELS, WB_ERR_ARG,
+             "wb_model_set_frontend: the reference recipe has 80 mel rows only (audio.rs:7); this model has %d", m->dims.n_mels);
   __atomic_store_n(&m->frontend, frontend, __ATOMIC_RELAXED);
   return WB_OK;
 }
@@ -153,6 +155,28 @@ int wb_mel_constants(double sample_rate, float* hann400, float* filters_80x201) 
   return WB_OK;
 }
 
+int wb_mel_filterbank(double sample_rate, int n_mels, float* filters) {
+  // host only: the dense [n_mels][201] filterbank of the frontend instance for n_mels rows, as its kernel uses it
+  WB_REQUIRE(filters, WB_ERR_ARG, "wb_mel_filterbank: null argument");
+  WB_REQUIRE(n_mels == MEL_N_MELS || n_mels == MEL128_N_MELS, WB_ERR_ARG, "wb_mel_filterbank: n_mels %d is neither 80 nor 128",
+             n_mels);
+  memset(filters, 0, sizeof(float) * n_mels * MEL_N_BINS);
+  if (n_mels == MEL_N_MELS) {
+    auto t = std::make_unique<MelTables>();
+    WB_REQUIRE(mel_tables_build(sample_rate, t.get()) == 0, WB_ERR_SHAPE,
+               "mel filterbank for sample_rate %g has a row wider than %d taps", sample_rate, MEL_MAX_TAPS);
+    for (int m = 0; m < n_mels; m++)
+      for (int k = 0; k < t->tap_len[m]; k++) filters[m * MEL_N_BINS + t->tap_start[m] + k] = t->tap_w[m * MEL_MAX_TAPS + k];
+    return WB_OK;
+  }
+  auto t = std::make_unique<MelTables128>();
+  WB_REQUIRE(mel_tables_build(sample_rate, t.get()) == 0, WB_ERR_SHAPE,
+             "mel filterbank for sample_rate %g has a row wider than %d taps", sample_rate, MEL128_MAX_TAPS);
+  for (int m = 0; m < n_mels; m++)
+    for (int k = 0; k < t->tap_len[m]; k++) filters[m * MEL_N_BINS + t->tap_start[m] + k] = t->tap_w[m * MEL128_MAX_TAPS + k];
+  return WB_OK;
+}
+
 int wb_mel_dft_table(float* table_402x400) {
   // host only: the reference recipe's DFT operand (audio.rs:348-364) as mel_dft.hip uses it, before padding
   WB_REQUIRE(table_402x400, WB_ERR_ARG, "wb_mel_dft_table: null argument");
@@ -171,9 +195,23 @@ int wb_prep_audio(int device, const float* pcm, int64_t n, double sample_rate, f
   return wb_prep_audio_frontend(device, pcm, n, sample_rate, mel, n_frames, WB_FRONTEND_FFT);
 }
 
+static int prep_audio_impl(int device, const float* pcm, int64_t n, double sample_rate, int n_mels, float* mel,
+                           int64_t* n_frames, int frontend);
+
 int wb_prep_audio_frontend(int device, const float* pcm, int64_t n, double sample_rate, float* mel, int64_t* n_frames,
                            int frontend) {
+  return prep_audio_impl(device, pcm, n, sample_rate, MEL_N_MELS, mel, n_frames, frontend);
+}
+
+int wb_prep_audio_mels(int device, const float* pcm, int64_t n, double sample_rate, int n_mels, float* mel,
+                       int64_t* n_frames) {
+  return prep_audio_impl(device, pcm, n, sample_rate, n_mels, mel, n_frames, WB_FRONTEND_FFT);
+}
+
+static int prep_audio_impl(int device, const float* pcm, int64_t n, double sample_rate, int n_mels, float* mel,
+                           int64_t* n_frames, int frontend) {
   WB_REQUIRE(pcm && mel, WB_ERR_ARG, "wb_prep_audio: null argument");
+  WB_REQUIRE(n_mels == MEL_N_MELS || n_mels == MEL128_N_MELS, WB_ERR_ARG, "wb_prep_audio: n_mels %d is neither 80 nor 128", n_mels);
   WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
              "wb_prep_audio: frontend %d is neither 0 (FFT) nor 1 (reference recipe)", frontend);
   WB_REQUIRE(n >= MEL_N_FFT, WB_ERR_SHAPE, "prep_audio: %lld samples < n_fft = 400 (audio.rs:292)", (long long)n);
@@ -181,21 +219,21 @@ int wb_prep_audio_frontend(int device, const float* pcm, int64_t n, double sampl
   wb::GpuTurn turn(device);
   WB_HIP(hipSetDevice(device));
   MelFrontend fe;
-  WB_TRY(get_mel_frontend(device, sample_rate, frontend, &fe));
+  WB_TRY(get_mel_frontend(device, sample_rate, frontend, n_mels, &fe));
   const int T = (int)(n / MEL_HOP);
   DevMem d_pcm, d_out, d_win, d_max;
   WB_TRY(d_pcm.alloc((size_t)n * 4));
-  WB_TRY(d_out.alloc((size_t)80 * T * 4));
+  WB_TRY(d_out.alloc((size_t)n_mels * T * 4));
   WB_TRY(d_win.alloc(sizeof(MelWindow)));
   WB_TRY(d_max.alloc((size_t)mel_bmax_stride(T) * 2 * 4));
   MelWindow w{0, (int32_t)n, T, T, 0};
   hipStream_t st = nullptr;
   WB_HIP(hipMemcpyAsync(d_pcm.p, pcm, (size_t)n * 4, hipMemcpyHostToDevice, st));
   WB_HIP(hipMemcpyAsync(d_win.p, &w, sizeof(w), hipMemcpyHostToDevice, st));
-  launch_mel_frontend(st, fe, d_pcm.as<float>(), d_win.as<MelWindow>(), 1, T, d_out.as<float>(), (int64_t)80 * T, T,
+  launch_mel_frontend(st, fe, d_pcm.as<float>(), d_win.as<MelWindow>(), 1, T, d_out.as<float>(), (int64_t)n_mels * T, T,
                       d_max.as<float>(), 0, T);
   WB_HIP(hipGetLastError());
-  WB_HIP(hipMemcpyAsync(mel, d_out.p, (size_t)80 * T * 4, hipMemcpyDeviceToHost, st));
+  WB_HIP(hipMemcpyAsync(mel, d_out.p, (size_t)n_mels * T * 4, hipMemcpyDeviceToHost, st));
   WB_HIP(hipStreamSynchronize(st));
   if (n_frames) *n_frames = T;
   return WB_OK;
@@ -214,7 +252,19 @@ int wb_waveform_to_mels_dev_frontend(int device, const float* pcm_dev, int64_t n
                                      const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
                                      int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
                                      int32_t* frames_out, int32_t iters, double* elapsed_ms, int32_t frontend) {
+  return wb_waveform_to_mels_dev_mels(device, pcm_dev, n_samples, sample_rate, starts, lens, n_windows, clip_frames, padding,
+                                      mel_dev, win_stride, row_stride, frames_out, iters, elapsed_ms, MEL_N_MELS, frontend);
+}
+
+int wb_waveform_to_mels_dev_mels(int device, const float* pcm_dev, int64_t n_samples, double sample_rate,
+                                 const int64_t* starts, const int64_t* lens, int32_t n_windows, int32_t clip_frames,
+                                 int32_t padding, float* mel_dev, int64_t win_stride, int32_t row_stride,
+                                 int32_t* frames_out, int32_t iters, double* elapsed_ms, int32_t n_mels, int32_t frontend) {
   WB_REQUIRE(pcm_dev && starts && lens && mel_dev && n_windows > 0, WB_ERR_ARG, "wb_waveform_to_mels_dev: bad argument");
+  WB_REQUIRE(n_mels == MEL_N_MELS || n_mels == MEL128_N_MELS, WB_ERR_ARG,
+             "wb_waveform_to_mels_dev: n_mels %d is neither 80 nor 128", (int)n_mels);
+  WB_REQUIRE(n_mels == MEL_N_MELS || frontend != WB_FRONTEND_REFERENCE, WB_ERR_ARG,
+             "wb_waveform_to_mels_dev: the reference recipe has 80 mel rows only (audio.rs:7)");
   WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
              "wb_waveform_to_mels_dev: frontend %d is neither 0 (FFT) nor 1 (reference recipe)", frontend);
   WB_REQUIRE(clip_frames > 0 && padding >= 0 && iters >= 1, WB_ERR_ARG, "wb_waveform_to_mels_dev: bad clip/padding/iters");
@@ -233,12 +283,12 @@ int wb_waveform_to_mels_dev_frontend(int device, const float* pcm_dev, int64_t n
     if (frames_out) frames_out[w] = T;
     maxF = std::max(maxF, nf); maxT = std::max(maxT, T);
   }
-  WB_REQUIRE(row_stride >= maxT && row_stride % 4 == 0 && win_stride >= (int64_t)80 * row_stride, WB_ERR_ARG,
+  WB_REQUIRE(row_stride >= maxT && row_stride % 4 == 0 && win_stride >= (int64_t)n_mels * row_stride, WB_ERR_ARG,
              "wb_waveform_to_mels_dev: row_stride %d must be a multiple of 4 and >= %d frames", row_stride, maxT);
   wb::GpuTurn turn(device);
   WB_HIP(hipSetDevice(device));
   MelFrontend fe;
-  WB_TRY(get_mel_frontend(device, sample_rate, frontend, &fe));
+  WB_TRY(get_mel_frontend(device, sample_rate, frontend, n_mels, &fe));
   DevMem d_win, d_max;
   WB_TRY(d_win.alloc(wins.size() * sizeof(MelWindow)));
   WB_TRY(d_max.alloc((size_t)n_windows * mel_bmax_stride(maxF) * 2 * 4));
@@ -277,13 +327,13 @@ int wb_forward_encoder(wb_model* m, const float* mel, int B, int T, float* out) 
   hipStream_t st = m->stream;
   const int d = m->dims.n_audio_state, C = (T - 1) / 2 + 1;
   // device mel rows are padded to a multiple of 4 floats
-  const int Ts = (T + 3) & ~3;
-  WB_TRY(sc->io_a.ensure((size_t)B * 80 * Ts * 4));
+  const int Ts = (T + 3) & ~3, NMEL = m->dims.n_mels;
+  WB_TRY(sc->io_a.ensure((size_t)B * NMEL * Ts * 4));
   WB_TRY(sc->io_b.ensure((size_t)B * C * d * 4));
-  WB_HIP(hipMemcpy2DAsync(sc->io_a.p, (size_t)Ts * 4, mel, (size_t)T * 4, (size_t)T * 4, (size_t)B * 80,
+  WB_HIP(hipMemcpy2DAsync(sc->io_a.p, (size_t)Ts * 4, mel, (size_t)T * 4, (size_t)T * 4, (size_t)B * NMEL,
                           hipMemcpyHostToDevice, st));
   MelBatch mb;
-  mb.mel = sc->io_a.as<float>(); mb.win_stride = (int64_t)80 * Ts; mb.row_stride = Ts; mb.T.assign(B, T);
+  mb.mel = sc->io_a.as<float>(); mb.win_stride = (int64_t)NMEL * Ts; mb.row_stride = Ts; mb.T.assign(B, T);
   EncoderOut eo;
   WB_TRY(run_encoder(m, st, sc->ws, mb, sc->io_b.as<float>(), &eo));
   WB_HIP(hipMemcpyAsync(out, sc->io_b.p, (size_t)B * C * d * 4, hipMemcpyDeviceToHost, st));
@@ -332,13 +382,13 @@ int wb_forward(wb_model* m, const float* mel, int B, int T, const int32_t* token
   WB_HIP(hipSetDevice(m->device));
   wb_model* sc = m;
   hipStream_t st = m->stream;
-  const int d = m->dims.n_audio_state, C = (T - 1) / 2 + 1, Ts = (T + 3) & ~3;
-  WB_TRY(sc->io_a.ensure((size_t)B * 80 * Ts * 4));
+  const int d = m->dims.n_audio_state, C = (T - 1) / 2 + 1, Ts = (T + 3) & ~3, NMEL = m->dims.n_mels;
+  WB_TRY(sc->io_a.ensure((size_t)B * NMEL * Ts * 4));
   WB_TRY(sc->io_b.ensure((size_t)B * C * d * 4));
-  WB_HIP(hipMemcpy2DAsync(sc->io_a.p, (size_t)Ts * 4, mel, (size_t)T * 4, (size_t)T * 4, (size_t)B * 80,
+  WB_HIP(hipMemcpy2DAsync(sc->io_a.p, (size_t)Ts * 4, mel, (size_t)T * 4, (size_t)T * 4, (size_t)B * NMEL,
                           hipMemcpyHostToDevice, st));
   MelBatch mb;
-  mb.mel = sc->io_a.as<float>(); mb.win_stride = (int64_t)80 * Ts; mb.row_stride = Ts; mb.T.assign(B, T);
+  mb.mel = sc->io_a.as<float>(); mb.win_stride = (int64_t)NMEL * Ts; mb.row_stride = Ts; mb.T.assign(B, T);
   EncoderOut eo;
   WB_TRY(run_encoder(m, st, sc->ws, mb, sc->io_b.as<float>(), &eo));
   return decoder_common(m, sc, st, tokens, B, L, sc->io_b.as<float>(), C, logits);

@@ -18,23 +18,24 @@ GpuTurn::GpuTurn(int device) {
   if (sw::gpu_turn()) lk = std::unique_lock<std::recursive_mutex>(mu[device < 0 ? 0 : device & 63]);
 }
 
-int get_mel_tables(int device, double sample_rate, const MelTables** out_dev) {
+template <class Tabs, int MAX_TAPS>
+static int get_mel_tables_t(int device, double sample_rate, const Tabs** out_dev) {
   static std::mutex mu;
-  static std::map<std::pair<int, double>, MelTables*> cache;
+  static std::map<std::pair<int, double>, Tabs*> cache;
   std::lock_guard<std::mutex> lk(mu);
   auto key = std::make_pair(device, sample_rate);
   auto it = cache.find(key);
   if (it != cache.end()) { *out_dev = it->second; return WB_OK; }
-  auto host = std::make_unique<MelTables>();
+  auto host = std::make_unique<Tabs>();
   WB_REQUIRE(mel_tables_build(sample_rate, host.get()) == 0, WB_ERR_SHAPE,
-             "mel filterbank for sample_rate %g has a row wider than %d taps", sample_rate, MEL_MAX_TAPS);
-  MelTables* dev = nullptr;
+             "mel filterbank for sample_rate %g has a row wider than %d taps", sample_rate, MAX_TAPS);
+  Tabs* dev = nullptr;
   WB_HIP(hipSetDevice(device));
-  WB_HIP(hipMalloc(&dev, sizeof(MelTables)));
+  WB_HIP(hipMalloc(&dev, sizeof(Tabs)));
   {  // (once per (device, rate); on a stream of its own: a legacy-stream copy fails while another thread captures a step graph)
     hipStream_t ts = nullptr;
     WB_HIP(hipStreamCreateWithFlags(&ts, hipStreamNonBlocking));
-    const hipError_t e1 = hipMemcpyAsync(dev, host.get(), sizeof(MelTables), hipMemcpyHostToDevice, ts);
+    const hipError_t e1 = hipMemcpyAsync(dev, host.get(), sizeof(Tabs), hipMemcpyHostToDevice, ts);
     const hipError_t e2 = hipStreamSynchronize(ts);
     (void)hipStreamDestroy(ts);
     WB_HIP(e1);
@@ -43,6 +44,12 @@ int get_mel_tables(int device, double sample_rate, const MelTables** out_dev) {
   cache[key] = dev;
   *out_dev = dev;
   return WB_OK;
+}
+int get_mel_tables(int device, double sample_rate, const MelTables** out_dev) {
+  return get_mel_tables_t<MelTables, MEL_MAX_TAPS>(device, sample_rate, out_dev);
+}
+int get_mel_tables(int device, double sample_rate, const MelTables128** out_dev) {
+  return get_mel_tables_t<MelTables128, MEL128_MAX_TAPS>(device, sample_rate, out_dev);
 }
 
 // The reference recipe's DFT table, transposed to [400][MEL_DFT_ROWS_PAD] (666 KB), once per device.
@@ -75,10 +82,17 @@ static int get_mel_dft_table(int device, const float** out_dev) {
   return WB_OK;
 }
 
-int get_mel_frontend(int device, double sample_rate, int frontend, MelFrontend* out) {
+int get_mel_frontend(int device, double sample_rate, int frontend, int n_mels, MelFrontend* out) {
   WB_REQUIRE(frontend == WB_FRONTEND_FFT || frontend == WB_FRONTEND_REFERENCE, WB_ERR_ARG,
              "log-mel frontend %d: 0 (FFT) or 1 (reference recipe)", frontend);
+  WB_REQUIRE(n_mels == MEL_N_MELS || n_mels == MEL128_N_MELS, WB_ERR_ARG, "log-mel frontend: n_mels %d is neither 80 nor 128",
+             n_mels);
+  WB_REQUIRE(n_mels == MEL_N_MELS || frontend == WB_FRONTEND_FFT, WB_ERR_ARG,
+             "the reference recipe has 80 mel rows only (audio.rs:7): no reference frontend at n_mels %d", n_mels);
   out->frontend = frontend;
+  out->n_mels = n_mels;
+  out->tabs = nullptr; out->tabs128 = nullptr; out->dft_tab = nullptr;
+  if (n_mels == MEL128_N_MELS) return get_mel_tables(device, sample_rate, &out->tabs128);
   WB_TRY(get_mel_tables(device, sample_rate, &out->tabs));
   out->dft_tab = nullptr;
   if (frontend == WB_FRONTEND_REFERENCE) WB_TRY(get_mel_dft_table(device, &out->dft_tab));
@@ -95,10 +109,14 @@ void launch_mel_frontend(hipStream_t st, const MelFrontend& fe, const float* pcm
     launch_mel_dft_finalize(st, wins_dev, n_windows, out, win_stride, row_stride, bmax_dev, max_frames);
     return;
   }
-  launch_mel_spectrogram(st, pcm, wins_dev, n_windows, max_frames, fe.tabs, out, win_stride, row_stride, bmax_dev, pad,
-                         pad_limit);
+  if (fe.n_mels == MEL128_N_MELS)
+    launch_mel_spectrogram(st, pcm, wins_dev, n_windows, max_frames, fe.tabs128, out, win_stride, row_stride, bmax_dev, pad,
+                           pad_limit);
+  else
+    launch_mel_spectrogram(st, pcm, wins_dev, n_windows, max_frames, fe.tabs, out, win_stride, row_stride, bmax_dev, pad,
+                           pad_limit);
   if (between) between();
-  launch_mel_finalize(st, wins_dev, n_windows, out, win_stride, row_stride, bmax_dev, max_frames);
+  launch_mel_finalize(st, wins_dev, n_windows, out, win_stride, row_stride, bmax_dev, max_frames, fe.n_mels);
 }
 
 // Developer tool (WHISPER_HIP_ENC_TRACE=<dir>): stream-ordered device copies of every stage of an encoder pass, written to
@@ -318,12 +336,12 @@ int run_encoder_unguarded(wb_model* m, hipStream_t st, Workspace& ws, const MelB
   float *x1 = ws.x1.as<float>(), *x = ws.x.as<float>(), *h = ws.h.as<float>(), *qkv = ws.qkv.as<float>(),
         *att = ws.att.as<float>(), *hm = ws.hm.as<float>();
 
-  // conv1 + GELU (mod.rs:243): implicit GEMM over [T, 240] x [240, d], output position-major [T, d]
+  // conv1 + GELU (mod.rs:243): implicit GEMM over [T, 3 n_mels] x [3 n_mels, d], output position-major [T, d]
   {
     GemmArgs g;
     g.A = mb.mel; g.a_desc = ws.desc1.as<RowDesc>(); g.conv1_tstride = mb.row_stride;
     g.B = m->conv1.w; g.ldb = d; g.C = x1; g.ldc = d; g.bias = m->conv1.b;
-    g.M = rows1; g.N = d; g.K = 240; g.act = ACT_GELU;
+    g.M = rows1; g.N = d; g.K = m->conv1.k; g.act = ACT_GELU;
     trace_stage(st, "mel", mb.mel, (size_t)nw * mb.win_stride * 4);
     WB_TRY(gemm(m, st, g, nullptr));
     trace_stage(st, "conv1", x1, (size_t)rows1 * d * 4);

@@ -8,7 +8,7 @@
 
 namespace wb {
 
-// Geometry of a batch of mel windows laid out [n_windows][80][row_stride]; T[w] = frames incl. padding.
+// Geometry of a batch of mel windows laid out [n_windows][n_mels][row_stride] (n_mels: the model's); T[w] = frames incl. padding.
 struct MelBatch {
   const float* mel = nullptr;      // device
   int64_t win_stride = 0;          // floats between windows
@@ -107,15 +107,19 @@ int gemm_dispatch(const wb_model* m, hipStream_t st, const GemmArgs& a, int ldwt
 
 // Process-wide mel constant tables for (device, sample_rate).
 int get_mel_tables(int device, double sample_rate, const MelTables** out_dev);
+int get_mel_tables(int device, double sample_rate, const MelTables128** out_dev);
 
 // The log-mel frontend of one call: K1 (mel.hip, WB_FRONTEND_FFT) or the reference recipe (mel_dft.hip,
 // WB_FRONTEND_REFERENCE), with its device tables (cached per device).  Every PCM entry point launches through here.
 struct MelFrontend {
   int frontend = WB_FRONTEND_FFT;
+  int n_mels = MEL_N_MELS;          // 80, or 128 (K1 only: the reference has no 128-row recipe)
   const MelTables* tabs = nullptr;
+  const MelTables128* tabs128 = nullptr;   // n_mels == 128
   const float* dft_tab = nullptr;   // reference recipe only: [400][MEL_DFT_ROWS_PAD]
 };
-int get_mel_frontend(int device, double sample_rate, int frontend, MelFrontend* out);
+// n_mels other than 80 / 128, or the reference recipe at 128 rows -> WB_ERR_ARG
+int get_mel_frontend(int device, double sample_rate, int frontend, int n_mels, MelFrontend* out);
 // main kernel + finalize; `between` (optional) runs after the main launch (developer trace stages)
 void launch_mel_frontend(hipStream_t st, const MelFrontend& fe, const float* pcm, const MelWindow* wins_dev, int n_windows,
                          int max_frames, float* out, int64_t win_stride, int row_stride, float* bmax_dev, int pad,

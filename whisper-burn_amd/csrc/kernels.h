@@ -45,6 +45,9 @@ bool prof_take_events(hipEvent_t* start, hipEvent_t* stop);
 // ---- mel frontend (mel.hip) ---------------------------------------------------------
 constexpr int MEL_N_FFT = 400, MEL_HOP = 160, MEL_N_MELS = 80, MEL_N_BINS = 201, MEL_MAX_TAPS = 16;
 
+// the 128-row geometry (large-v3 and later): at 16 kHz its Slaney rows have at most 9 taps; 12 keeps whole float4 chunks
+constexpr int MEL128_N_MELS = 128, MEL128_MAX_TAPS = 12;
+
 struct MelTables {            // device-resident constants, built once per (device, sample_rate)
   float hann[400];            // audio.rs:272-278
   float2 tw[400];             // W_400^{n2*k1}, index n2*20+k1
@@ -52,8 +55,17 @@ struct MelTables {            // device-resident constants, built once per (devi
   int tap_len[80];
   float tap_w[80 * MEL_MAX_TAPS];
 };
-// Host-side construction (f32 op order of the reference); returns 0 / -1 if a row has > MAX_TAPS taps.
+struct MelTables128 {         // the same for 128 mel rows
+  float hann[400];
+  float2 tw[400];
+  int tap_start[MEL128_N_MELS];
+  int tap_len[MEL128_N_MELS];
+  float tap_w[MEL128_N_MELS * MEL128_MAX_TAPS];
+};
+// Host-side construction; returns 0 / -1 if a row has more taps than its table holds.  80 rows: the f32 op order of the
+// reference.  128 rows: designed in f64 (the Slaney construction as librosa evaluates it), rounded once to f32.
 int mel_tables_build(double sample_rate, MelTables* host_out);
+int mel_tables_build(double sample_rate, MelTables128* host_out);
 
 struct MelWindow {            // one window of PCM
   int64_t pcm_off;            // offset (samples) of the window start in the PCM buffer
@@ -70,9 +82,13 @@ int mel_bmax_stride(int max_frames);
 void launch_mel_spectrogram(hipStream_t st, const float* pcm, const MelWindow* wins_dev, int n_windows,
                             int max_frames, const MelTables* tabs_dev, float* out, int64_t win_stride,
                             int row_stride, float* bmax_dev, int pad, int pad_limit);
+// ... the 128-row instance: out[w] is [128][row_stride]
+void launch_mel_spectrogram(hipStream_t st, const float* pcm, const MelWindow* wins_dev, int n_windows,
+                            int max_frames, const MelTables128* tabs_dev, float* out, int64_t win_stride,
+                            int row_stride, float* bmax_dev, int pad, int pad_limit);
 // clamp fix-up: max(x, gmax - 8) (audio.rs:52) on the tiles that need it (normally none: the log-mel is written once)
 void launch_mel_finalize(hipStream_t st, const MelWindow* wins_dev, int n_windows, float* out, int64_t win_stride,
-                         int row_stride, const float* bmax_dev, int max_frames);
+                         int row_stride, const float* bmax_dev, int max_frames, int n_mels = MEL_N_MELS);
 // reference-recipe frontend (mel_dft.hip): dense f32 DFT on MFMA against the reference's own f32 angle table
 // (audio.rs:348-364); same window / output / bmax geometry as the two launches above, but the main kernel stores the
 // un-normalised log10 and the finalize applies relu(x - m8) + m8 and (x + 4) / 4 to every emitted element.

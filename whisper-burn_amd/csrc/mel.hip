@@ -41,9 +41,24 @@ constexpr int MEL_THREADS = PAIRS * 20;   // 320
 constexpr int FROW = 426;        // LDS floats per frame row: 2*FROW = 852 >= 840 (U) and 852 % 32 == 20
 constexpr int UROW = 21;         // padded row (float2) of the 20x20 intermediate
 constexpr int PB_OFF = 209;      // frame b's power spectrum: 209 = 17 mod 64, so stage 4's lane = frame reads hit 32 distinct banks
-constexpr int OT_OFF = 416;      // a pair's 2 x 80 outputs live behind its two power spectra
-constexpr int TAP_OFF = 576;     // ... and behind them the taps of mel rows 5p .. 5p+4 (5 x 16 floats) for stage 4
+constexpr int OT_OFF = 416;      // a pair's 2 x n_mels outputs live behind its two power spectra
 constexpr int BMAX_OFF = 800;    // the block-maximum scratch (pair 0's region)
+
+// What depends on the number of mel rows (stages 3 tail to 5, the zero-pad tiles, the fix-up): one instance per geometry.
+//   80 rows:  16 taps per row, 5 rows per pair region, stage 4 deals 10 groups x 8 rows (every half-wave busy);
+//             TAP_OFF = 576 (the taps of mel rows 5p .. 5p+4, 5 x 16 floats), row metadata at 656 .. 665
+//   128 rows: 12 taps per row (the 16 kHz bank has <= 9), 8 rows per pair region, stage 4 deals 8 groups x 16 rows = the
+//             rows of two whole pair regions (10 groups do not divide 128; the fifth wave sits stage 4 out -- the row-slots
+//             of work are the same 128); TAP_OFF = 672 (8 x 12 floats), row metadata at 768 .. 783
+// Both end in front of BMAX_OFF; Pf[s0 + t] of a padded tap reaches at most 209 + 200 + TAPS - 1 < 2 FROW: inside the region.
+struct Mel80 {
+  typedef MelTables Tabs;
+  static constexpr int NM = 80, TAPS = MEL_MAX_TAPS, RPP = 5, RPG = 8;
+};
+struct Mel128 {
+  typedef MelTables128 Tabs;
+  static constexpr int NM = 128, TAPS = MEL128_MAX_TAPS, RPP = 8, RPG = 16;
+};
 
 struct cpx { float re, im; };
 
@@ -185,13 +200,22 @@ __device__ __forceinline__ void dft20(cpx (&xc)[20]) {
   for (int i = 0; i < 20; i++) xc[i] = cpx{x[i].x, x[i].y};
 }
 
+template <class G>
 __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogram_kernel(
-    const float* __restrict__ pcm, const MelWindow* __restrict__ wins, const MelTables* __restrict__ tabs,
+    const float* __restrict__ pcm, const MelWindow* __restrict__ wins, const typename G::Tabs* __restrict__ tabs,
     float* __restrict__ out, int64_t win_stride, int row_stride, float* __restrict__ gmax, int bmax_stride, int pad,
     int pad_limit) {
   // 16 x 852 floats = 54 528 B: three blocks per CU (163 584 B of the 160 KiB); every stage aliases the same
-  // pair-private regions (frame rows -> U -> Z -> power spectra + this pair's 2 x 80 outputs)
+  // pair-private regions (frame rows -> U -> Z -> power spectra + this pair's 2 x n_mels outputs)
   __shared__ __attribute__((aligned(16))) float lds[PAIRS * 2 * FROW];
+  constexpr int NM = G::NM, TAPS = G::TAPS, RPP = G::RPP, RPG = G::RPG;
+  constexpr int TAP_OFF = OT_OFF + 2 * NM, META_OFF = TAP_OFF + RPP * TAPS;
+  constexpr int NGRP = NM / RPG;                                   // stage 4: half-waves that own mel rows
+  constexpr int TAP_Q = NM * TAPS / 4, TAP_ITERS = (TAP_Q + MEL_THREADS - 1) / MEL_THREADS;   // float4 pieces of taps
+  static_assert(RPP * PAIRS == NM && NGRP * RPG == NM && NGRP * 32 <= MEL_THREADS && TAPS % 4 == 0 && NM <= MEL_THREADS,
+                "mel rows must divide over the pair regions and the stage-4 groups");
+  static_assert(META_OFF + 2 * RPP <= BMAX_OFF && BMAX_OFF + 16 <= 2 * FROW && PB_OFF + MEL_N_BINS - 1 + TAPS - 1 < 2 * FROW,
+                "outputs, taps and row metadata must fit inside the pair region");
 
   const MelWindow w = wins[blockIdx.y];
   const int f0 = blockIdx.x * FPB;
@@ -202,7 +226,7 @@ __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogra
     // fix-up pass only reads the tiles that hold real frames (blk < ceil(n_frames / FPB)), and with a large padding the
     // grid may be wider than the per-window stride of `gmax` (a pair written here could land in the next window's slots).
     float* oz = out + (int64_t)blockIdx.y * win_stride;
-    for (int e = tid; e < MEL_N_MELS * FPB; e += MEL_THREADS) {
+    for (int e = tid; e < NM * FPB; e += MEL_THREADS) {
       const int m = e / FPB, f = f0 + (e - m * FPB);
       if (f >= w.n_emit && f < zend) oz[(int64_t)m * row_stride + f] = 0.f;
     }
@@ -210,7 +234,6 @@ __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogra
   }
   const int N = w.n_samples;
   const float* x = pcm + w.pcm_off;
-  static_assert(MEL_N_MELS * MEL_MAX_TAPS == MEL_THREADS * 4, "one float4 of taps per thread");
 
   // ---- stage 0: the block's contiguous PCM span (31 hops + 400 = 5360 samples) is read ONCE, coalesced,
   // with reflect indexing at the window edges (audio.rs:297-306); every sample is scattered to the <= 3
@@ -303,11 +326,17 @@ __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogra
   __syncthreads();
   // ---- stage 3: split the packed transform, power spectrum of both frames ----
   // A[k] = (Z[k] + conj Z[400-k]) / 2,  B[k] = (Z[k] - conj Z[400-k]) / (2i)
-  // this thread's 4 of the 80 x 16 filterbank taps (+ start / length of row tid): requested here, they land under
-  // the unpack arithmetic and move to LDS next to the power spectra, so that stage 4's tap loop runs on LDS
-  // latency instead of one dependent global load per tap
-  const float4 tapq = *reinterpret_cast<const float4*>(&tabs->tap_w[tid * 4]);
-  const int tap_s0 = tid < MEL_N_MELS ? tabs->tap_start[tid] : 0, tap_n = tid < MEL_N_MELS ? tabs->tap_len[tid] : 0;
+  // this thread's 4 of the filterbank taps (80 x 16: one float4 per thread; 128 x 12: a second one for the first 64
+  // threads) (+ start / length of row tid): requested here, they land under the unpack arithmetic and move to LDS next
+  // to the power spectra, so that stage 4's tap loop runs on LDS latency instead of one dependent global load per tap
+  float4 tapq[TAP_ITERS];
+#pragma unroll
+  for (int i = 0; i < TAP_ITERS; i++) {
+    const int j = tid + i * MEL_THREADS;
+    tapq[i] = (i + 1) * MEL_THREADS <= TAP_Q || j < TAP_Q ? *reinterpret_cast<const float4*>(&tabs->tap_w[j * 4])
+                                                          : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const int tap_s0 = tid < NM ? tabs->tap_start[tid] : 0, tap_n = tid < NM ? tabs->tap_len[tid] : 0;
   float pa[11], pb[11];
 #pragma unroll
   for (int i = 0; i < 11; i++) {
@@ -328,43 +357,48 @@ __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogra
     if (k <= 200) { WB_SETTLE2(pa[i], pb[i]); P[k] = pa[i]; P[PB_OFF + k] = pb[i]; }
   }
   {
-    const int m = tid >> 2;                     // taps 4 tid .. 4 tid + 3 belong to mel row m
-    *reinterpret_cast<float4*>(&lds[(m / 5) * 2 * FROW + TAP_OFF + (m % 5) * MEL_MAX_TAPS + (tid & 3) * 4]) = tapq;
-    if (tid < MEL_N_MELS) {                     // (start, length) of row tid behind its pair region's taps
-      int* meta = reinterpret_cast<int*>(&lds[(tid / 5) * 2 * FROW + TAP_OFF + 5 * MEL_MAX_TAPS + (tid % 5) * 2]);
+    constexpr int PPR = TAPS / 4;               // pieces per mel row: taps 4 j .. 4 j + 3 belong to mel row j / PPR
+#pragma unroll
+    for (int i = 0; i < TAP_ITERS; i++) {
+      const int j = tid + i * MEL_THREADS, m = j / PPR;
+      if ((i + 1) * MEL_THREADS <= TAP_Q || j < TAP_Q)
+        *reinterpret_cast<float4*>(&lds[(m / RPP) * 2 * FROW + TAP_OFF + (m % RPP) * TAPS + (j % PPR) * 4]) = tapq[i];
+    }
+    if (tid < NM) {                             // (start, length) of row tid behind its pair region's taps
+      int* meta = reinterpret_cast<int*>(&lds[(tid / RPP) * 2 * FROW + META_OFF + (tid % RPP) * 2]);
       meta[0] = tap_s0; meta[1] = tap_n;
     }
   }
   __syncthreads();
   // ---- stage 4: sparse mel filterbank, log10, local max ----
-  // lane = frame, half-wave = group of 8 mel rows: the filter taps are uniform over each half-wave
+  // lane = frame, half-wave = group of RPG mel rows: the filter taps are uniform over each half-wave
   // (broadcast LDS reads), the power spectra are the lane's own frame
   const float LOG10_2 = 0.30102999566398119521f;    // log10(2)
   float lmax = -INFINITY, lmin = INFINITY;
-  {
-    const int f = tid & (FPB - 1), grp = tid >> 5;            // 10 groups x 8 rows
+  if (NGRP * 32 == MEL_THREADS || tid < NGRP * 32) {
+    const int f = tid & (FPB - 1), grp = tid >> 5;            // 10 groups x 8 rows / 8 groups x 16 rows
     float* fr_reg = lds + (f >> 1) * 2 * FROW;
     const float* Pf = fr_reg + (f & 1) * PB_OFF;
     const bool live = f0 + f < w.n_frames;
-    int s0v[8], lenv[8];
+    int s0v[RPG], lenv[RPG];
 #pragma unroll
-    for (int r = 0; r < 8; r++) {
-      const int m = grp * 8 + r;
-      const int* meta = reinterpret_cast<const int*>(&lds[(m / 5) * 2 * FROW + TAP_OFF + 5 * MEL_MAX_TAPS + (m % 5) * 2]);
+    for (int r = 0; r < RPG; r++) {
+      const int m = grp * RPG + r;
+      const int* meta = reinterpret_cast<const int*>(&lds[(m / RPP) * 2 * FROW + META_OFF + (m % RPP) * 2]);
       s0v[r] = meta[0]; lenv[r] = meta[1];
     }
-    // chunk-major: the eight rows of the group advance together (eight independent sums: their LDS reads are in flight
+    // chunk-major: the rows of the group advance together (eight / sixteen independent sums: their LDS reads are in flight
     // together -- a row-major loop waits for one row's chunk at a time: 1.09 -> 1.16 G frames/s, profiles/r04_h_mel_variants.txt); the trip count is the group's longest row,
     // taps past a row's length are stored as zeros and Pf[s0 + t] stays inside the pair's region (finite FFT leftovers)
-    float accv[8];
+    float accv[RPG];
     int nch = 0;
 #pragma unroll
-    for (int r = 0; r < 8; r++) { accv[r] = 0.f; nch = max(nch, (lenv[r] + 3) >> 2); }
+    for (int r = 0; r < RPG; r++) { accv[r] = 0.f; nch = max(nch, (lenv[r] + 3) >> 2); }
     for (int c = 0; c < nch; c++) {
 #pragma unroll
-      for (int r = 0; r < 8; r++) {
-        const int m = grp * 8 + r;
-        const float* tw = lds + (m / 5) * 2 * FROW + TAP_OFF + (m % 5) * MEL_MAX_TAPS;
+      for (int r = 0; r < RPG; r++) {
+        const int m = grp * RPG + r;
+        const float* tw = lds + (m / RPP) * 2 * FROW + TAP_OFF + (m % RPP) * TAPS;
         const float4 w4 = *reinterpret_cast<const float4*>(tw + 4 * c);
         const float* pp = Pf + s0v[r] + 4 * c;
 #if !defined(HIPEMU) && !defined(WB_MEL_NO_ASM)
@@ -380,8 +414,8 @@ __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogra
       }
     }
 #pragma unroll
-    for (int r = 0; r < 8; r++) {
-      const int m = grp * 8 + r;
+    for (int r = 0; r < RPG; r++) {
+      const int m = grp * RPG + r;
       const float acc = accv[r];
       // tensor_max_scalar(x, 1e-10) = relu(x - 1e-10) + 1e-10 (helper.rs:8-10); log10 = ln/ln10 (:24-27)
       // ln(x) / ln 10 (helper.rs:24-27) through the hardware log2 (v_log_f32, <= 1 ulp; the argument is >= 1e-10, normal):
@@ -407,19 +441,21 @@ __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogra
     gmax[((int64_t)blockIdx.y * bmax_stride + blockIdx.x) * 2] = bm;
     gmax[((int64_t)blockIdx.y * bmax_stride + blockIdx.x) * 2 + 1] = bn;
   }
-  // ---- stage 5: coalesced store of the [80][32] tile ----
+  // ---- stage 5: coalesced store of the [n_mels][32] tile ----
   float* o = out + (int64_t)blockIdx.y * win_stride + f0;
   const int nf = min(FPB, w.n_emit - f0);
   if (nf == FPB && (row_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-    // full tile: 80 rows x 8 pieces of 16 bytes, two per thread
+    // full tile: n_mels rows x 8 pieces of 16 bytes: 80 rows two per thread, 128 rows three and a fourth for 64 threads
+    constexpr int ST_Q = NM * FPB / 4;
 #pragma unroll
-    for (int i = 0; i < MEL_N_MELS * FPB / 4 / MEL_THREADS; i++) {
+    for (int i = 0; i < (ST_Q + MEL_THREADS - 1) / MEL_THREADS; i++) {
       const int e = tid + i * MEL_THREADS, m = e >> 3, f = (e & 7) * 4;
       const float* a = lds + (f >> 1) * 2 * FROW + OT_OFF + 2 * m;     // frames f, f+1 in one pair region, f+2, f+3 in the next
-      *reinterpret_cast<float4*>(o + (int64_t)m * row_stride + f) = make_float4(a[0], a[1], a[2 * FROW], a[2 * FROW + 1]);
+      if ((i + 1) * MEL_THREADS <= ST_Q || e < ST_Q)
+        *reinterpret_cast<float4*>(o + (int64_t)m * row_stride + f) = make_float4(a[0], a[1], a[2 * FROW], a[2 * FROW + 1]);
     }
   } else {
-    for (int e = tid; e < MEL_N_MELS * FPB; e += MEL_THREADS) {
+    for (int e = tid; e < NM * FPB; e += MEL_THREADS) {
       int m = e / FPB, f = e - m * FPB;
       if (f < nf) o[(int64_t)m * row_stride + f] = lds[(f >> 1) * 2 * FROW + OT_OFF + 2 * m + (f & 1)];
       else if (f0 + f >= w.n_emit && f0 + f < zend) o[(int64_t)m * row_stride + f] = 0.f;
@@ -432,6 +468,7 @@ __global__ __launch_bounds__(MEL_THREADS, WB_MEL_MIN_BLOCKS) void mel_spectrogra
 // its block exits after reading the per-tile (max, min) pairs -- for ordinary audio that is every tile, so the log-mel
 // is written ONCE.  A tile that does dip below (digital silence, 80 dB under the loudest bin of the window) is
 // rewritten: x < max - 8 gives (relu(x - m8) + m8 + 4) / 4 = (m8 + 4) / 4 exactly as the reference computes it.
+template <int NM>
 __global__ __launch_bounds__(256) void mel_clamp_fixup_kernel(const MelWindow* __restrict__ wins, float* __restrict__ out,
                                                               int64_t win_stride, int row_stride,
                                                               const float* __restrict__ bmm, int bmax_stride) {
@@ -452,7 +489,7 @@ __global__ __launch_bounds__(256) void mel_clamp_fixup_kernel(const MelWindow* _
   const float yfloor = (m8 + 4.0f) / 4.0f;                               // (relu(x - m8) + m8 + 4) / 4 for x < m8
   const int f0 = blk * FPB, nf = min(FPB, wins[w].n_emit - f0);
   float* o = out + (int64_t)w * win_stride + f0;
-  for (int e = tid; e < MEL_N_MELS * FPB; e += 256) {
+  for (int e = tid; e < NM * FPB; e += 256) {
     const int m = e / FPB, f = e - m * FPB;
     if (f < nf) {
       float* q = o + (int64_t)m * row_stride + f;
@@ -495,15 +532,27 @@ void launch_mel_spectrogram(hipStream_t st, const float* pcm, const MelWindow* w
                             int row_stride, float* bmax_dev, int pad, int pad_limit) {
   // tiles up to the last frame OR the last zero-padding frame of the longest window
   dim3 grid((std::min(max_frames + pad, std::max(pad_limit, max_frames)) + FPB - 1) / FPB, n_windows);
-  hipLaunchKernelGGL(mel_spectrogram_kernel, grid, dim3(MEL_THREADS), 0, st, pcm, wins_dev, tabs_dev, out,
+  hipLaunchKernelGGL(mel_spectrogram_kernel<Mel80>, grid, dim3(MEL_THREADS), 0, st, pcm, wins_dev, tabs_dev, out,
+                     win_stride, row_stride, bmax_dev, mel_bmax_stride(max_frames), pad, pad_limit);
+}
+
+void launch_mel_spectrogram(hipStream_t st, const float* pcm, const MelWindow* wins_dev, int n_windows,
+                            int max_frames, const MelTables128* tabs_dev, float* out, int64_t win_stride,
+                            int row_stride, float* bmax_dev, int pad, int pad_limit) {
+  dim3 grid((std::min(max_frames + pad, std::max(pad_limit, max_frames)) + FPB - 1) / FPB, n_windows);
+  hipLaunchKernelGGL(mel_spectrogram_kernel<Mel128>, grid, dim3(MEL_THREADS), 0, st, pcm, wins_dev, tabs_dev, out,
                      win_stride, row_stride, bmax_dev, mel_bmax_stride(max_frames), pad, pad_limit);
 }
 
 void launch_mel_finalize(hipStream_t st, const MelWindow* wins_dev, int n_windows, float* out, int64_t win_stride,
-                         int row_stride, const float* bmax_dev, int max_frames) {
+                         int row_stride, const float* bmax_dev, int max_frames, int n_mels) {
   dim3 grid((max_frames + FPB - 1) / FPB, n_windows);
-  hipLaunchKernelGGL(mel_clamp_fixup_kernel, grid, dim3(256), 0, st, wins_dev, out, win_stride, row_stride, bmax_dev,
-                     mel_bmax_stride(max_frames));
+  if (n_mels == MEL128_N_MELS)
+    hipLaunchKernelGGL(mel_clamp_fixup_kernel<MEL128_N_MELS>, grid, dim3(256), 0, st, wins_dev, out, win_stride, row_stride,
+                       bmax_dev, mel_bmax_stride(max_frames));
+  else
+    hipLaunchKernelGGL(mel_clamp_fixup_kernel<MEL_N_MELS>, grid, dim3(256), 0, st, wins_dev, out, win_stride, row_stride,
+                       bmax_dev, mel_bmax_stride(max_frames));
 }
 
 void launch_pcm_s16_to_f32(hipStream_t st, const int16_t* src, int64_t n, float* dst) {
@@ -521,19 +570,23 @@ void launch_fill_f32(hipStream_t st, float* p, int64_t n, float v) {
 // The filterbank follows the f32 op order of audio.rs:67-143 / :178-266 (scalars are cast to
 // f32 before each tensor op, as burn-tch does), so it matches what the reference builds on
 // device for every window -- here once per process.
-int mel_tables_build(double sample_rate, MelTables* t) {
-  memset(t, 0, sizeof(*t));
+static void mel_window_tables(float* hann, float2* tw) {
   // Hann: sin(n * f32(pi/400))^2 in f32 (audio.rs:272-278)
   const float step = (float)(M_PI / 400.0);
   for (int n = 0; n < 400; n++) {
     float s = sinf((float)n * step);
-    t->hann[n] = s * s;
+    hann[n] = s * s;
   }
   for (int n2 = 0; n2 < 20; n2++)
     for (int k1 = 0; k1 < 20; k1++) {
       double a = -2.0 * M_PI * (double)(n2 * k1) / 400.0;
-      t->tw[n2 * 20 + k1] = make_float2((float)cos(a), (float)sin(a));
+      tw[n2 * 20 + k1] = make_float2((float)cos(a), (float)sin(a));
     }
+}
+
+int mel_tables_build(double sample_rate, MelTables* t) {
+  memset(t, 0, sizeof(*t));
+  mel_window_tables(t->hann, t->tw);
   // mel_frequencies_device (audio.rs:178-196) with hz_to_mel (:198-230) in f64 on the host
   auto hz_to_mel = [](double f) {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
@@ -580,6 +633,41 @@ int mel_tables_build(double sample_rate, MelTables* t) {
     t->tap_start[i] = s;
     t->tap_len[i] = len;
     for (int k = 0; k < len; k++) t->tap_w[i * MEL_MAX_TAPS + k] = W[i][s + k];
+  }
+  return 0;
+}
+
+// The 128-row bank (large-v3 and later) is DESIGNED in f64 and rounded once to f32: the Slaney construction as librosa
+// evaluates it, which is what those checkpoints were trained against.  The f32 op order above is not good enough there: its
+// narrow low-frequency triangles lose up to 5e-6 of a weight to cancellation in the ramps, 1.9e-4 on the log-mel.
+int mel_tables_build(double sample_rate, MelTables128* t) {
+  memset(t, 0, sizeof(*t));
+  mel_window_tables(t->hann, t->tw);
+  constexpr int NM = MEL128_N_MELS;
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+  auto hz_to_mel = [&](double f) { return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp; };
+  const double min_mel = hz_to_mel(0.0), max_mel = hz_to_mel(sample_rate * 0.5);
+  double mel_f[NM + 2];
+  for (int i = 0; i < NM + 2; i++) {
+    const double mel = (double)i * ((max_mel - min_mel) / (double)(NM + 1)) + min_mel;
+    mel_f[i] = mel >= min_log_mel ? 1000.0 * exp(logstep * (mel - min_log_mel)) : f_sp * mel;
+  }
+  for (int i = 0; i < NM; i++) {
+    const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1], enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+    float row[MEL_N_BINS];
+    int s = -1, e = -1;
+    for (int j = 0; j < MEL_N_BINS; j++) {
+      const double ff = (double)j * (sample_rate / 400.0);
+      const double lower = -(mel_f[i] - ff) / fd0, upper = (mel_f[i + 2] - ff) / fd1;
+      row[j] = (float)(std::max(0.0, std::min(lower, upper)) * enorm);
+      if (row[j] != 0.f) { if (s < 0) s = j; e = j; }
+    }
+    if (s < 0) { s = 0; e = -1; }
+    const int len = e - s + 1;
+    if (len > MEL128_MAX_TAPS) return -1;
+    t->tap_start[i] = s;
+    t->tap_len[i] = len;
+    for (int k = 0; k < len; k++) t->tap_w[i * MEL128_MAX_TAPS + k] = row[s + k];
   }
   return 0;
 }

@@ -257,7 +257,10 @@ int build_model(TensorMap& tm, int device, int compute_dtype, wb_model** out) {
              WB_ERR_SHAPE, "State size %d must be a multiple of head size", d);   // mod.rs:393-398
   WB_REQUIRE(d / D.n_audio_head == 64 && d / D.n_text_head == 64, WB_ERR_SHAPE,
              "this engine is built for head size 64 (every Whisper preset); got %d", d / D.n_audio_head);
-  WB_REQUIRE(d % 64 == 0 && D.n_mels == 80, WB_ERR_SHAPE, "n_state must be a multiple of 64 and n_mels 80");
+  WB_REQUIRE(d % 64 == 0, WB_ERR_SHAPE, "n_state must be a multiple of 64");
+  WB_REQUIRE(D.n_mels == MEL_N_MELS || D.n_mels == MEL128_N_MELS, WB_ERR_SHAPE,
+             "n_mels %d: this engine has a log-mel frontend for 80 and for 128 mel rows", D.n_mels);
+  const int NMEL = D.n_mels;
   m->qk_scale = (float)std::pow((double)d / (double)D.n_audio_head, -0.25);   // mod.rs:503
 
   // ---- arena image ----
@@ -265,15 +268,15 @@ int build_model(TensorMap& tm, int device, int compute_dtype, wb_model** out) {
   {
     const float *w, *b;
     WB_TRY(B.get("encoder/conv1/weight", 3, &w, &s));
-    WB_REQUIRE(s[0] == d && s[1] == 80 && s[2] == 3, WB_ERR_SHAPE, "encoder/conv1/weight: expected [%d,80,3]", d);
+    WB_REQUIRE(s[0] == d && s[1] == NMEL && s[2] == 3, WB_ERR_SHAPE, "encoder/conv1/weight: expected [%d,%d,3]", d, NMEL);
     WB_TRY(B.get("encoder/conv1/bias", 1, &b, &s));
     WB_REQUIRE(s[0] == d, WB_ERR_SHAPE, "encoder/conv1/bias: expected [%d]", d);
-    conv1.k = 240; conv1.n = d;
-    conv1.w = B.reserve((size_t)240 * d);
+    conv1.k = 3 * NMEL; conv1.n = d;
+    conv1.w = B.reserve((size_t)3 * NMEL * d);
     for (int co = 0; co < d; co++)
-      for (int ci = 0; ci < 80; ci++)
+      for (int ci = 0; ci < NMEL; ci++)
         for (int kk = 0; kk < 3; kk++)
-          B.host[conv1.w + (size_t)(ci * 3 + kk) * d + co] = w[((size_t)co * 80 + ci) * 3 + kk];
+          B.host[conv1.w + (size_t)(ci * 3 + kk) * d + co] = w[((size_t)co * NMEL + ci) * 3 + kk];
     conv1.b = B.reserve(d); memcpy(&B.host[conv1.b], b, sizeof(float) * d);
     WB_TRY(B.get("encoder/conv2/weight", 3, &w, &s));
     WB_REQUIRE(s[0] == d && s[1] == d && s[2] == 3, WB_ERR_SHAPE, "encoder/conv2/weight: expected [%d,%d,3]", d, d);

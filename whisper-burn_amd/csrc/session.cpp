@@ -185,11 +185,12 @@ int session_encode_pcm(wb_session* s, const float* pcm, int64_t n_pcm, const int
   }
   const int Ts = (maxT + 3) & ~3;
   MelFrontend fe;
-  WB_TRY(get_mel_frontend(m->device, s->sample_rate, __atomic_load_n(&m->frontend, __ATOMIC_RELAXED), &fe));
+  const int NMEL = m->dims.n_mels;
+  WB_TRY(get_mel_frontend(m->device, s->sample_rate, __atomic_load_n(&m->frontend, __ATOMIC_RELAXED), NMEL, &fe));
   if (!pcm_on_device) WB_TRY(s->pcm.ensure((size_t)(hi - lo) * 4));
   WB_TRY(s->wins.ensure(wins.size() * sizeof(MelWindow)));
   WB_TRY(s->gmax.ensure((size_t)s->W * mel_bmax_stride(maxF) * 2 * 4));
-  WB_TRY(s->mel.ensure((size_t)s->W * 80 * Ts * 4));
+  WB_TRY(s->mel.ensure((size_t)s->W * NMEL * Ts * 4));
   if (!pcm_on_device && sw::pcm_stage()) {
     const size_t nb = (size_t)(hi - lo) * 4;
     if (s->pcm_stage_bytes < nb) {
@@ -218,9 +219,9 @@ int session_encode_pcm(wb_session* s, const float* pcm, int64_t n_pcm, const int
   if (!pcm_on_device && (trace_extra & 1)) enc_trace_stage(s->st, "pcm", s->pcm.p, (size_t)(hi - lo) * 4);
   {
     ScopedTimer tm(s->st, 0);
-    launch_mel_frontend(s->st, fe, pcm_dev, s->wins.as<MelWindow>(), s->W, maxF, s->mel.as<float>(), (int64_t)80 * Ts, Ts,
+    launch_mel_frontend(s->st, fe, pcm_dev, s->wins.as<MelWindow>(), s->W, maxF, s->mel.as<float>(), (int64_t)NMEL * Ts, Ts,
                         s->gmax.as<float>(), s->padding, Ts, [&]() {
-                          if (trace_extra & 2) enc_trace_stage(s->st, "mel0", s->mel.p, (size_t)s->W * 80 * Ts * 4);
+                          if (trace_extra & 2) enc_trace_stage(s->st, "mel0", s->mel.p, (size_t)s->W * NMEL * Ts * 4);
                           if (trace_extra & 4)
                             enc_trace_stage(s->st, "gmax", s->gmax.p, (size_t)s->W * mel_bmax_stride(maxF) * 2 * 4);
                         });
@@ -229,7 +230,7 @@ int session_encode_pcm(wb_session* s, const float* pcm, int64_t n_pcm, const int
   }
   WB_HIP(hipGetLastError());
   MelBatch mb;
-  mb.mel = s->mel.as<float>(); mb.win_stride = (int64_t)80 * Ts; mb.row_stride = Ts; mb.T = s->T;
+  mb.mel = s->mel.as<float>(); mb.win_stride = (int64_t)NMEL * Ts; mb.row_stride = Ts; mb.T = s->T;
   return session_finish_encode(s, mb, defer_guard);
 }
 
@@ -338,13 +339,13 @@ int wb_session_begin_mel(wb_model* m, const float* mel, const int32_t* T, int n_
     s->T[w] = std::min(T[w], clip) + padding;   // transcribe.rs:171-177
     maxT = std::max(maxT, s->T[w]);
   }
-  const int Ts = (maxT + 3) & ~3;
-  std::vector<float> host((size_t)n_windows * 80 * Ts, 0.f);
+  const int Ts = (maxT + 3) & ~3, NMEL = m->dims.n_mels;
+  std::vector<float> host((size_t)n_windows * NMEL * Ts, 0.f);
   const float* src = mel;
   for (int w = 0; w < n_windows; w++) {
     const int keep = s->T[w] - padding;
-    for (int r = 0; r < 80; r++) memcpy(&host[((size_t)w * 80 + r) * Ts], src + (size_t)r * T[w], (size_t)keep * 4);
-    src += (size_t)80 * T[w];
+    for (int r = 0; r < NMEL; r++) memcpy(&host[((size_t)w * NMEL + r) * Ts], src + (size_t)r * T[w], (size_t)keep * 4);
+    src += (size_t)NMEL * T[w];
   }
   int rc = s->mel.ensure(host.size() * 4);
   if (rc == WB_OK && (hipMemcpyAsync(s->mel.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, s->st) != hipSuccess ||
@@ -354,7 +355,7 @@ int wb_session_begin_mel(wb_model* m, const float* mel, const int32_t* T, int n_
   }
   if (rc == WB_OK) {
     MelBatch mb;
-    mb.mel = s->mel.as<float>(); mb.win_stride = (int64_t)80 * Ts; mb.row_stride = Ts; mb.T = s->T;
+    mb.mel = s->mel.as<float>(); mb.win_stride = (int64_t)NMEL * Ts; mb.row_stride = Ts; mb.T = s->T;
     rc = session_finish_encode(s, mb);
   }
   if (rc != WB_OK) { wb_session_free(s); return rc; }

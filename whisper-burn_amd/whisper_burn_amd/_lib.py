@@ -83,6 +83,7 @@ SIGNATURES = {
     "wb_max_waveform_samples": (C.c_int64, [C.c_int64]),
     "wb_prep_audio": (C.c_int, [C.c_int, c_float_p, C.c_int64, C.c_double, c_float_p, c_int64_p]),
     "wb_prep_audio_frontend": (C.c_int, [C.c_int, c_float_p, C.c_int64, C.c_double, c_float_p, c_int64_p, C.c_int]),
+    "wb_prep_audio_mels": (C.c_int, [C.c_int, c_float_p, C.c_int64, C.c_double, C.c_int, c_float_p, c_int64_p]),
     "wb_model_load_burn_record": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "wb_burn_record_read": (C.c_int, [C.c_char_p, C.c_char_p, TENSOR_FN, C.c_void_p]),
     "wb_wav_info": (C.c_int, [C.c_char_p, c_int64_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
@@ -98,6 +99,9 @@ SIGNATURES = {
     "wb_waveform_to_mels_dev_frontend": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_double, c_int64_p, c_int64_p,
                                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                                    c_int32_p, C.c_int32, c_double_p, C.c_int32]),
+    "wb_waveform_to_mels_dev_mels": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_double, c_int64_p, c_int64_p,
+                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                               c_int32_p, C.c_int32, c_double_p, C.c_int32, C.c_int32]),
     "wb_forward_encoder": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_float_p]),
     "wb_forward_decoder": (C.c_int, [C.c_void_p, c_int32_p, C.c_int, C.c_int, c_float_p, C.c_int, c_float_p]),
     "wb_forward": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_int32_p, C.c_int, c_float_p]),
@@ -235,6 +239,7 @@ SIGNATURES = {
     "wb_repetition_period": (C.c_int64, [c_int32_p, C.c_int64, C.c_int64]),
     "wb_find_repeated_tokens_index": (C.c_int, [c_int32_p, C.c_int64, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),
     "wb_mel_constants": (C.c_int, [C.c_double, c_float_p, c_float_p]),
+    "wb_mel_filterbank": (C.c_int, [C.c_double, C.c_int, c_float_p]),
     "wb_mel_dft_table": (C.c_int, [c_float_p]),
     "wb_profile_enable": (C.c_int, [C.c_int]),
     "wb_profile_read": (C.c_int, [c_double_p, C.c_int]),

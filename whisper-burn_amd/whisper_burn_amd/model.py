@@ -20,6 +20,7 @@ from ._lib import WbBeamParams, WbDecodeParams, WbDims, WbError, WbFallbackParam
 from .tokens import SpecialTokens
 
 WB_F32, WB_BF16 = 0, 1
+WB_ERR_ARG = -1
 WB_ERR_SHAPE = -2
 
 
@@ -485,20 +486,35 @@ def mel_dft_table() -> np.ndarray:
     return t
 
 
-def prep_audio(waveform, sample_rate: float = 16000.0, device: int = 0, frontend: str = "fft") -> np.ndarray:
-    """audio.rs:34: waveform [n_batch, n_samples] -> log-mel [n_batch, 80, n_samples // 160].
-    frontend="reference" computes the reference's own recipe (dense f32 DFT, wb_prep_audio_frontend)."""
+def mel_filterbank(sample_rate: float = 16000.0, n_mels: int = 80) -> np.ndarray:
+    """The dense [n_mels, 201] filterbank the frontend kernels use (host only, no GPU; wb_mel_filterbank): 80 rows in the
+    reference's f32 op order, 128 rows (large-v3 and later) designed in f64 and rounded once."""
+    f = np.empty((max(int(n_mels), 1), 201), dtype=np.float32)
+    check(_lib.load().wb_mel_filterbank(float(sample_rate), int(n_mels), _fp(f)))
+    return f
+
+
+def prep_audio(waveform, sample_rate: float = 16000.0, device: int = 0, frontend: str = "fft",
+               n_mels: int = 80) -> np.ndarray:
+    """audio.rs:34: waveform [n_batch, n_samples] -> log-mel [n_batch, n_mels, n_samples // 160].
+    frontend="reference" computes the reference's own recipe (dense f32 DFT, wb_prep_audio_frontend); it has 80 rows only.
+    n_mels=128 is the frontend of large-v3 and later (wb_prep_audio_mels)."""
     lib = _lib.load()
     fid = frontend_id(frontend)
+    if n_mels != 80 and fid != 0:
+        raise WbError(WB_ERR_ARG, "the reference recipe has 80 mel rows only")
     w = _f32(waveform)
     if w.ndim == 1:
         w = w[None]
     out = []
     for row in w:
         n = row.shape[0]
-        mel = np.empty((80, max(n // 160, 0)), dtype=np.float32)
+        mel = np.empty((max(int(n_mels), 1), max(n // 160, 0)), dtype=np.float32)
         nf = C.c_int64(0)
-        check(lib.wb_prep_audio_frontend(device, _fp(row), n, float(sample_rate), _fp(mel), C.byref(nf), fid))
+        if n_mels == 80:
+            check(lib.wb_prep_audio_frontend(device, _fp(row), n, float(sample_rate), _fp(mel), C.byref(nf), fid))
+        else:
+            check(lib.wb_prep_audio_mels(device, _fp(row), n, float(sample_rate), int(n_mels), _fp(mel), C.byref(nf)))
         out.append(mel)
     return np.stack(out)
 
@@ -572,15 +588,23 @@ def pcm_s16_to_f32_dev(src_ptr: int, n: int, dst_ptr: int, device: int = 0) -> N
 
 def waveform_to_mels_dev(pcm_ptr: int, n_samples: int, starts, lens, mel_ptr: int, win_stride: int, row_stride: int,
                          sample_rate: float = 16000.0, clip_frames: int = 1490, padding: int = 10, device: int = 0,
-                         iters: int = 1, frontend: str = "fft"):
-    """transcribe.rs:114-138 + :171-177 for a batch of windows, device pointers in and out.
-    Returns (frames per window, HIP-event milliseconds of all `iters` passes).  frontend: as `prep_audio`."""
+                         iters: int = 1, frontend: str = "fft", n_mels: int = 80):
+    """transcribe.rs:114-138 + :171-177 for a batch of windows, device pointers in and out; window w is written as
+    [n_mels, row_stride].  Returns (frames per window, HIP-event milliseconds of all `iters` passes).  frontend, n_mels:
+    as `prep_audio`."""
     fid = frontend_id(frontend)
     lib = _lib.load()
     st = np.ascontiguousarray(starts, dtype=np.int64)
     ln = np.ascontiguousarray(lens, dtype=np.int64)
     frames = np.zeros(len(st), dtype=np.int32)
     ms = C.c_double(0.0)
+    if n_mels != 80:
+        check(lib.wb_waveform_to_mels_dev_mels(device, C.c_void_p(pcm_ptr), n_samples, float(sample_rate),
+                                               st.ctypes.data_as(_lib.c_int64_p), ln.ctypes.data_as(_lib.c_int64_p),
+                                               len(st), clip_frames, padding, C.c_void_p(mel_ptr), win_stride,
+                                               row_stride, frames.ctypes.data_as(_lib.c_int32_p), iters, C.byref(ms),
+                                               int(n_mels), fid))
+        return frames, float(ms.value)
     check(lib.wb_waveform_to_mels_dev_frontend(device, C.c_void_p(pcm_ptr), n_samples, float(sample_rate),
                                                st.ctypes.data_as(_lib.c_int64_p), ln.ctypes.data_as(_lib.c_int64_p),
                                                len(st), clip_frames, padding, C.c_void_p(mel_ptr), win_stride,

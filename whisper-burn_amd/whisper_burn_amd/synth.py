@@ -14,22 +14,29 @@ from collections import OrderedDict
 import numpy as np
 from scipy.signal import lfilter
 
-# name -> (n_state, n_head, n_layer, n_vocab); n_mels=80, n_audio_ctx=1500, n_text_ctx=448
+# name -> (n_state, n_head, n_layer, n_vocab); n_mels=80, n_audio_ctx=1500, n_text_ctx=448 unless _PRESET_EXTRA says otherwise
 PRESETS = OrderedDict([
     ("tiny.en", (384, 6, 4, 51864)),
     ("base.en", (512, 8, 6, 51864)),
     ("small", (768, 12, 12, 51865)),
     ("medium", (1024, 16, 24, 51865)),
     ("large-v2", (1280, 20, 32, 51865)),
+    ("large-v3", (1280, 20, 32, 51866)),
+    ("large-v3-turbo", (1280, 20, 32, 51866)),
 ])
-_ALIASES = {"tiny_en": "tiny.en", "base_en": "base.en", "large_v2": "large-v2", "large": "large-v2"}
+# the 128-bin models; turbo keeps large-v3's 32 encoder layers over a 4-layer decoder
+_PRESET_EXTRA = {"large-v3": dict(n_mels=128), "large-v3-turbo": dict(n_mels=128, n_text_layer=4)}
+_ALIASES = {"tiny_en": "tiny.en", "base_en": "base.en", "large_v2": "large-v2", "large": "large-v2",
+            "large_v3": "large-v3", "large_v3_turbo": "large-v3-turbo", "turbo": "large-v3-turbo"}
 
 
 def preset_dims(name: str) -> dict:
     name = _ALIASES.get(name, name)
     d, h, n_layer, v = PRESETS[name]
-    return dict(n_mels=80, n_audio_ctx=1500, n_audio_state=d, n_audio_head=h, n_audio_layer=n_layer,
+    dims = dict(n_mels=80, n_audio_ctx=1500, n_audio_state=d, n_audio_head=h, n_audio_layer=n_layer,
                 n_vocab=v, n_text_ctx=448, n_text_state=d, n_text_head=h, n_text_layer=n_layer)
+    dims.update(_PRESET_EXTRA.get(name, {}))
+    return dims
 
 
 def preset_seed(name: str) -> int:
@@ -318,11 +325,13 @@ def synth_preset(name: str, logit_scale: float = 6.0, **overrides):
     return synth_weights(preset_dims(name), preset_seed(name), logit_scale, **overrides)
 
 
-def micro_dims(n_state=128, n_head=2, n_layer=2, n_vocab=1031, n_audio_ctx=1500, n_text_ctx=448) -> dict:
-    """A small model at the real head size (d_h = 64) for fast oracle runs."""
-    return dict(n_mels=80, n_audio_ctx=n_audio_ctx, n_audio_state=n_state, n_audio_head=n_head,
+def micro_dims(n_state=128, n_head=2, n_layer=2, n_vocab=1031, n_audio_ctx=1500, n_text_ctx=448, n_mels=80,
+               n_text_layer=None) -> dict:
+    """A small model at the real head size (d_h = 64) for fast oracle runs.  n_layer: encoder layers, and decoder layers
+    too unless n_text_layer says otherwise (large-v3-turbo's shape); n_mels: 80, or 128 (large-v3 and later)."""
+    return dict(n_mels=n_mels, n_audio_ctx=n_audio_ctx, n_audio_state=n_state, n_audio_head=n_head,
                 n_audio_layer=n_layer, n_vocab=n_vocab, n_text_ctx=n_text_ctx, n_text_state=n_state,
-                n_text_head=n_head, n_text_layer=n_layer)
+                n_text_head=n_head, n_text_layer=n_layer if n_text_layer is None else n_text_layer)
 
 
 def synth_audio(n_samples: int, seed: int, sample_rate: int = 16000) -> np.ndarray:
